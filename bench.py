@@ -1,6 +1,15 @@
 """Benchmark of the PowerSGD hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--sets S]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: set-up, W warm-up steps, K timed steps,
+the output dump if asked for, the result line. ``--full`` adds every other block described
+below (warm loop, rooflines, the other configs, the world-size > 1 path, CPU baseline, at
+N > 1 the IPC exchange block and the parity check). ``--dump-outputs DIR`` writes what the last
+timed step returned (``out_<i>.npy``) and left in the gradients (``residual_<i>.npy``) as
+float32, a fixed seeded sample of each tensor when the whole is larger than 48 MiB; inputs and
+the codec's initial state are seeded, so two builds can be compared file by file.
 
 One step = one ``PowerSGD.aggregate`` over the synthetic gradients of the workload
 (compressed matrices: power iterations + factor all-reduce + fused residual/output
@@ -17,10 +26,11 @@ Cache state. The headline is COLD: the timed loop rotates over S (default 4) ind
 gradient sets, so between two uses of one set the other S-1 sets (gradients read and rewritten,
 fresh outputs written) stream > 256 MiB through the chip and the set is out of the 256 MiB
 Infinity Cache, as after a real backward pass. The same loop on ONE set (warm: the 102 MB
-ResNet-50 set plus its output fit the Infinity Cache) is reported beside it.
+ResNet-50 set plus its output fit the Infinity Cache) is reported beside it with ``--full``.
 
 Prints ONE JSON line on rank 0. ``value`` = gradient bytes processed by all ranks per second
-(GB/s, cold). ``roofline`` = the final pass, the dominant kernel: k_final_odd (the last odd
+(GB/s, cold); ``ms_per_step`` = wall milliseconds of one timed step. The rest needs ``--full``:
+``roofline`` = the final pass, the dominant kernel: k_final_odd (the last odd
 power iteration fused with the residual/output writes) or k_apply, timed with HIP events that
 the library records on the launch stream around every such launch, over a second pass of the
 same cold rotation. ``cpu_baseline`` = the CPU oracle (bit-identical restatement of the
@@ -57,15 +67,25 @@ def parse():
                     help="experiments only: override the config's num_iters_per_step (reported in config)")
     ap.add_argument("--mode", default="both", choices=["both", "cold", "warm"],
                     help="profiling runs: time only one cache state (the headline needs 'both' or 'cold')")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the warm loop, the final-pass roofline passes, the post-backward, "
+                         "rank4/cfg4/cfg5 and world-size > 1 path blocks, the CPU baseline and (N > 1) the IPC "
+                         "exchange block and the cross-GPU parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and residuals as DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the rank4/cfg4/cfg5 blocks and (N = 1) the world-size > 1 path block")
+                    help="--full: skip the rank4/cfg4/cfg5 blocks and (N = 1) the world-size > 1 path block")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-parity", action="store_true",
-                    help="N > 1: skip the cross-GPU parity check of the W > 1 transports (after the timed blocks)")
+                    help="--full, N > 1: skip the cross-GPU parity check of the W > 1 transports (after the timed "
+                         "blocks)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous + world-size report only (no codec; CPU-testable with gloo)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def numel(s):
@@ -164,14 +184,17 @@ def launch_ranks(a) -> int:
     return subprocess.run(cmd).returncode
 
 
-def timed(fn, steps, world, dev):
-    """Barrier + synchronize on both sides of `steps` calls; max wall time over ranks."""
+def timed(fn, steps, world, dev, keep=None):
+    """Barrier + synchronize on both sides of `steps` calls; max wall time over ranks. What the
+    last call returned is appended to `keep` (only the last: a result held across the next call
+    would keep the codec from reusing its output buffer, which a plain caller's loop does)."""
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for k in range(steps):
+    for k in range(steps - 1):
         fn(k)
+    last = fn(steps - 1) if steps > 0 else None
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
@@ -180,7 +203,35 @@ def timed(fn, steps, world, dev):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if keep is not None:
+        keep.append(last)
     return elapsed
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: float32 bytes written at most (outputs and residuals, half each)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, outs, residuals):
+    """The last timed step's results as float32 .npy files: `out_<i>` = the aggregated gradient
+    aggregate() returned for tensor i, `residual_<i>` = what it left in the caller's gradient
+    (the error-feedback residual, written in place). Past DUMP_BYTES every tensor is cut to the
+    same fraction of its elements, at flat indices drawn by a generator seeded with DUMP_SEED
+    and the tensor's position (CPU generator), so two builds dump the same elements."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    total = sum(o.numel() for o in outs)
+    frac = min(1.0, DUMP_BYTES / 2 / 4 / max(total, 1))
+    for i, (o, r) in enumerate(zip(outs, residuals)):
+        o, r = o.reshape(-1), r.reshape(-1)
+        if frac < 1.0:
+            g = torch.Generator().manual_seed(DUMP_SEED + i)
+            idx = torch.randint(0, o.numel(), (max(1, int(o.numel() * frac)),), generator=g).sort().values
+            idx = idx.to(o.device)
+            o, r = o[idx], r[idx]
+        np.save(os.path.join(path, f"out_{i:04d}.npy"), o.float().cpu().numpy())
+        np.save(os.path.join(path, f"residual_{i:04d}.npy"), r.float().cpu().numpy())
 
 
 def main():
@@ -228,7 +279,18 @@ def main():
             print(f"bench.py: process group reports {got} ranks, --gpus {a.gpus}", file=sys.stderr)
             sys.exit(3)
     dev = torch.device("cuda", local)
-    out = measure(a, a.config, world, rank, dev, backend, a.mode)
+    out = measure(a, a.config, world, rank, dev, backend, a.mode, dump=a.dump_outputs)
+    if a.full:
+        full_blocks(a, out, world, rank, dev, backend)
+    if rank == 0:
+        sys.stdout.flush()
+        os.write(json_fd, (json.dumps(out) + "\n").encode())
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def full_blocks(a, out, world, rank, dev, backend):
+    """--full: every block beside the headline, added to the result line `out`."""
     if world > 1 and os.environ.get("PSGD_BENCH_IPC", "1") == "1" and "PSGD_COMM" not in os.environ:
         # the same step with every factor all-reduce as a one-shot sum over IPC exchange buffers
         # (device-side flags, no collective library): beside the RCCL headline, not instead of it
@@ -268,11 +330,6 @@ def main():
         out["cpu_baseline"] = cpu_baseline(c, a.cpu_seconds)
     elif rank == 0:
         out["cpu_baseline"] = None
-    if rank == 0:
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
-    if world > 1:
-        torch.distributed.destroy_process_group()
 
 
 EXTRA_BLOCKS = (("rank4", "cfg3_resnet50_r4"), ("cfg4", "cfg4_llama_r2_bf16"), ("cfg5", "cfg5_lstm_r1_i4"))
@@ -521,12 +578,11 @@ def env_block(a, world, rank, dev, backend, env):
 def one_rank_group(a, dev):
     """cfg3 and cfg2 through PowerSGD.aggregate with torch.distributed initialised as ONE RCCL
     rank on this GPU: is_distributed() is True, so the exact multi-GPU code path runs."""
-    import socket
+    import tempfile
 
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    torch.distributed.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1,
+    # a file rendezvous (no loopback port to pick first and lose to another process)
+    store_dir = tempfile.TemporaryDirectory()
+    torch.distributed.init_process_group("nccl", init_method=f"file://{store_dir.name}/init", rank=0, world_size=1,
                                          device_id=dev)
     try:
         res = {"note": "world-size>1 code path on one GPU via a 1-rank RCCL process group (per-rank compute floor; "
@@ -549,11 +605,14 @@ def one_rank_group(a, dev):
         return res
     finally:
         torch.distributed.destroy_process_group()
+        store_dir.cleanup()
 
 
-def measure(a, cfg_name, world, rank, dev, backend, mode, dist_path=False):
-    """One workload: warm-up, the timed cold (rotating sets) and warm loops, the final-pass
-    roofline pass. `world` is the job's world size (1 for the 1-rank group)."""
+def measure(a, cfg_name, world, rank, dev, backend, mode, dist_path=False, dump=None):
+    """One workload: warm-up and the timed headline loop (cold: rotating sets; warm with --mode
+    warm); with --full also the other cache state's loop and the final-pass roofline passes.
+    `world` is the job's world size (1 for the 1-rank group). `dump`: directory that receives the
+    headline loop's last step (dump_outputs), written before anything else runs."""
     from powersgd_amd import Config, PowerSGD
 
     CONFIGS = CONFIGS_()
@@ -589,9 +648,17 @@ def measure(a, cfg_name, world, rank, dev, backend, mode, dist_path=False):
                                f"{[r for r, b in enumerate(bad) if b]}")
 
     # timed regions: K plain steps each (no instrumentation inside); cold = rotating sets
-    do_cold, do_warm = mode in ("both", "cold"), mode in ("both", "warm")
-    cold = timed(lambda k: psgd.aggregate(sets[k % S]), a.steps, world, dev) if do_cold else None
-    warm = timed(lambda k: psgd.aggregate(sets[0]), a.steps, world, dev) if do_warm else None
+    do_cold, do_warm = mode in ("both", "cold"), mode == "warm" or (mode == "both" and a.full)
+    first_head = codec.step_counter
+    last = []
+    cold = timed(lambda k: psgd.aggregate(sets[k % S]), a.steps, world, dev, last) if do_cold else None
+    if dump and do_cold and rank == 0:
+        dump_outputs(dump, last[0], sets[(a.steps - 1) % S])
+    del last[:]  # the output buffer is free for reuse again
+    warm = timed(lambda k: psgd.aggregate(sets[0]), a.steps, world, dev, last) if do_warm else None
+    if dump and not do_cold and rank == 0:
+        dump_outputs(dump, last[0], sets[0])
+    del last[:]
 
     # roofline passes: the same K steps again with HIP events around every final-pass launch,
     # recorded by the library on the launch stream
@@ -607,10 +674,12 @@ def measure(a, cfg_name, world, rank, dev, backend, mode, dist_path=False):
         # the algorithmic bytes below are the whole step's final pass
         return total_ms / a.steps, first, launches / a.steps
 
-    apply_ms_cold, first_cold, lps_cold = kernel_pass(lambda k: k % S) if do_cold else (None, None, None)
-    apply_ms_warm, first_warm, lps_warm = kernel_pass(lambda k: 0) if do_warm else (None, None, None)
+    apply_ms_cold, first_cold, lps_cold = kernel_pass(lambda k: k % S) if do_cold and a.full else (None, None, None)
+    apply_ms_warm, first_warm, lps_warm = kernel_pass(lambda k: 0) if do_warm and a.full else (None, None, None)
     if first_cold is None:
         first_cold = first_warm
+    if first_cold is None:  # no roofline pass: the forms of the timed steps themselves
+        first_cold = first_head
 
     multi = world > 1 or dist_path
     s = 2 if dtype == torch.bfloat16 else 4
@@ -666,9 +735,10 @@ def measure(a, cfg_name, world, rank, dev, backend, mode, dist_path=False):
                    "buckets": len(codec._buckets) if codec._buckets else 1,
                    "backend": (backend if multi else None)},
         "per_rank_GBs": round(value / world, 3),
-        "roofline": roof(apply_ms_cold, "cold", lps_cold) if do_cold else roof(apply_ms_warm, "warm", lps_warm),
         "step_roofline": step_roof(head),
     }
+    if a.full:
+        out["roofline"] = roof(apply_ms_cold, "cold", lps_cold) if do_cold else roof(apply_ms_warm, "warm", lps_warm)
     if codec._ipc_open:
         out["ipc_timed_out"] = codec.ipc_status()
         codec.close_ipc()

@@ -19,7 +19,7 @@ def test_bench_two_ranks_one_device_parity():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PSGD_COMM")}
     env.update(PSGD_BENCH_ONE_DEVICE="1", PSGD_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--sets", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=420)
+                        "--sets", "2", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=420)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout

@@ -5,7 +5,6 @@ of an 8-GPU run (K-term final pass, write-only output pass, flat pack /W inside 
 collective). Checked per step against the CPU oracle (bit-identical to the reference) at
 world size 1. Spawned in a child process so the process group does not leak into other tests."""
 import os
-import socket
 
 import pytest
 import torch
@@ -19,7 +18,7 @@ def _rel(a, b, scale):
     return float((a.double().cpu() - b.double().cpu()).norm()) / max(float(scale.double().norm()), 1e-30)
 
 
-def _worker(_, port, cfg, steps, env=None):
+def _worker(_, initfile, cfg, steps, env=None):
     os.environ.update(env or {})  # plan knobs, read at plan creation
     from oracle import powersgd_oracle as O
     from powersgd_amd import Config, PowerSGD, _lib
@@ -27,7 +26,7 @@ def _worker(_, port, cfg, steps, env=None):
 
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
-    torch.distributed.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1,
+    torch.distributed.init_process_group("nccl", init_method=f"file://{initfile}", rank=0, world_size=1,
                                          device_id=dev)
     try:
         c = CONFIGS[cfg]
@@ -62,19 +61,15 @@ def _worker(_, port, cfg, steps, env=None):
 
 
 @pytest.mark.parametrize("cfg", ["cfg3_resnet50_r4", "cfg2_resnet50_r1", "cfg5_lstm_r1_i4", "cfg4_llama_r2_bf16"])
-def test_rccl_step_one_rank_vs_oracle(cfg):
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    torch.multiprocessing.spawn(_worker, args=(port, cfg, 3), nprocs=1, join=True)
+def test_rccl_step_one_rank_vs_oracle(cfg, tmp_path):
+    # a file rendezvous in the test's own directory: a loopback port picked here could be taken
+    # by another process before the child listens on it
+    torch.multiprocessing.spawn(_worker, args=(str(tmp_path / "init"), cfg, 3), nprocs=1, join=True)
 
 
-def test_rccl_kterm_own_row_blocks_vs_oracle():
+def test_rccl_kterm_own_row_blocks_vs_oracle(tmp_path):
     """The K-term final pass on its own row blocks (psgd_plan.cpp tiles_fin_kt, MatDesc::
     fin_rows_kt) at an odd block size, 5000 elements: ragged against every ResNet-50 row length,
     beside the projection form's default blocks of the same plan."""
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    torch.multiprocessing.spawn(_worker, args=(port, "cfg2_resnet50_r1", 2, {"PSGD_FIN_ELEMS_KT": "5000"}),
-                                nprocs=1, join=True)
+    torch.multiprocessing.spawn(_worker, args=(str(tmp_path / "init"), "cfg2_resnet50_r1", 2,
+                                               {"PSGD_FIN_ELEMS_KT": "5000"}), nprocs=1, join=True)

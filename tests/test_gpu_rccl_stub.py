@@ -11,7 +11,6 @@ world size to the output pass — the negative controls below prove the test can
 Each case runs in a spawned child (its own environment, stub and process group)."""
 import ctypes
 import os
-import socket
 
 import pytest
 import torch
@@ -37,17 +36,17 @@ def _spec(cfg):
     return CONFIGS[cfg] if cfg in CONFIGS else WIDE[cfg]
 
 
-def _port():
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        return sk.getsockname()[1]
+def _init(tmp_path):
+    """Rendezvous of the child's one-rank group: a file store in the test's own directory (a
+    loopback port picked here could be taken by another process before the child listens)."""
+    return f"file://{tmp_path}/store"
 
 
 def _rel(a, b, scale):
     return float((a.double().cpu() - b.double().cpu()).norm()) / max(float(scale.double().norm()), 1e-30)
 
 
-def _run(cfg, world, steps, port, env):
+def _run(cfg, world, steps, init, env):
     """`steps` steps of cfg at world size `world` through the stub; returns per step the largest
     output / residual errors against W oracle workers and the stub's collective count."""
     os.environ["PSGD_RCCL_LIB_FORCE"] = STUB
@@ -60,7 +59,7 @@ def _run(cfg, world, steps, port, env):
 
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
-    torch.distributed.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1)
+    torch.distributed.init_process_group("gloo", init_method=init, rank=0, world_size=1)
     try:
         stub = ctypes.CDLL(STUB)  # the same handle the library opened: one call counter
         stub.psgd_stub_calls.restype = ctypes.c_longlong
@@ -104,8 +103,8 @@ def _run(cfg, world, steps, port, env):
         torch.distributed.destroy_process_group()
 
 
-def _positive(_, port, cfg, world, steps):
-    rep = _run(cfg, world, steps, port, {"PSGD_STUB_MODE": "sum"})
+def _positive(_, init, cfg, world, steps):
+    rep = _run(cfg, world, steps, init, {"PSGD_STUB_MODE": "sum"})
     c_iters = _spec(cfg)["iters"]
     for t, (eo, er, calls, nunc) in enumerate(rep):
         bf16 = _spec(cfg)["dtype"] == "bf16"
@@ -121,13 +120,13 @@ def _positive(_, port, cfg, world, steps):
 @pytest.mark.parametrize("cfg,world", [("cfg2_resnet50_r1", 4), ("cfg3_resnet50_r4", 4),
                                        ("cfg5_lstm_r1_i4", 8), ("cfg4_llama_r2_bf16", 2),
                                        ("wide16", 2), ("wide32", 4), ("wide16bf", 2)])
-def test_rccl_orchestration_world_w_vs_oracle(cfg, world):
+def test_rccl_orchestration_world_w_vs_oracle(cfg, world, tmp_path):
     """psgd_aggregate_comm at world W, 2 steps, vs W reference workers."""
-    torch.multiprocessing.spawn(_positive, args=(_port(), cfg, world, 2), nprocs=1, join=True)
+    torch.multiprocessing.spawn(_positive, args=(_init(tmp_path), cfg, world, 2), nprocs=1, join=True)
 
 
-def _negative(_, port, cfg, world, env, q):
-    rep = _run(cfg, world, 1, port, env)
+def _negative(_, init, cfg, world, env, q):
+    rep = _run(cfg, world, 1, init, env)
     q.put(max(rep[0][0], rep[0][1]))
 
 
@@ -140,12 +139,12 @@ def _negative(_, port, cfg, world, env, q):
     ("cfg5_lstm_r1_i4", 8, {"PSGD_STUB_MODE": "skip", "PSGD_STUB_SKIP_AT": "1"}),
     ("cfg5_lstm_r1_i4", 8, {"PSGD_STUB_MODE": "twice"})],
     ids=["twice", "skip-q", "skip-p", "skip-flat", "cfg5-skip-p1", "cfg5-twice"])
-def test_rccl_orchestration_negative_controls(cfg, world, env):
+def test_rccl_orchestration_negative_controls(cfg, world, env, tmp_path):
     """A collective library that reduces twice or drops one of the step's collectives must make
     the W-worker comparison fail (the positive test above is able to fail)."""
     ctx = torch.multiprocessing.get_context("spawn")
     q = ctx.Queue()
-    p = ctx.Process(target=_negative, args=(0, _port(), cfg, world, env, q))
+    p = ctx.Process(target=_negative, args=(0, _init(tmp_path), cfg, world, env, q))
     p.start()
     err = q.get(timeout=300)
     p.join(timeout=60)

@@ -12,7 +12,7 @@ import torch
 
 from oracle import powersgd_oracle as O
 from golden_io import checksums, config_grads, config_state0, load, manifest, scenario_inputs
-from powersgd_amd.workloads import CONFIGS
+from powersgd_amd.workloads import CONFIGS, hash_tensors
 
 MAN = manifest()
 
@@ -107,31 +107,24 @@ def test_oracle_config_checksums(cfg):
         assert ps.codec.q_flat.double().sum().item() == want[f"s{t}_q_sum"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/powersgd"), reason="reference not present")
-def test_oracle_matches_live_reference_random_shapes():
-    """Extra pin when the reference is on disk (dev container only)."""
-    import sys
-
-    sys.path.insert(0, "/root/reference")
-    try:
-        from powersgd import Config, PowerSGD
-    finally:
-        sys.path.remove("/root/reference")
+def test_oracle_matches_reference_random_shapes():
+    """The reference's recorded steps on a mixed shape set (F5, tests/golden/make_golden_random.py:
+    three (rank, iterations) cases, three steps each with error feedback): initial state, outputs
+    and residuals, bitwise."""
+    want = load("F5_random_shapes")
     shapes = [(40, 30), (40, 30), (7, 5, 2), (9,), (128, 3, 3), (5, 300)]
-    for rank, iters in ((1, 2), (3, 3), (2, 1)):
-        params = [torch.zeros(s) for s in shapes]
-        ref = PowerSGD(params, Config(rank, 1.5, iters, 0))
-        ora = O.policy_init(params, rank, 1.5, iters, 0)
-        g1 = [torch.randn(s) for s in shapes]
-        g2 = [g.clone() for g in g1]
-        for _ in range(3):
-            o1 = ref.aggregate(g1)
-            o2 = O.policy_step(ora, g2)
-            for a, b in zip(o1, o2):
-                assert torch.equal(a, b)
-            for a, b in zip(g1, g2):
-                assert torch.equal(a, b)
-            for a, b in zip(g1, g2):
-                noise = torch.randn(a.shape)
-                a.add_(noise)
-                b.add_(noise)
+    seen = set()
+    for ci, (rank, iters) in enumerate(((1, 2), (3, 3), (2, 1))):
+        ora = O.policy_init([torch.zeros(s) for s in shapes], rank, 1.5, iters, 0)
+        got = {f"c{ci}_p0": ora.codec.p_flat.numpy().copy(), f"c{ci}_q0": ora.codec.q_flat.numpy().copy()}
+        grads = [torch.from_numpy(f) for f in hash_tensors(shapes, seed=3000 + 10 * ci)]
+        for t in range(3):
+            outs = O.policy_step(ora, grads)
+            for i in range(len(shapes)):
+                got[f"c{ci}_s{t}_out_{i}"] = outs[i].numpy().copy()
+                got[f"c{ci}_s{t}_res_{i}"] = grads[i].numpy().copy()
+            for g, f in zip(grads, hash_tensors(shapes, seed=3000 + 10 * ci + t + 1)):
+                g.add_(torch.from_numpy(f))
+        _assert_same(got, {k: v for k, v in want.items() if k.startswith(f"c{ci}_")}, "F5 ")
+        seen |= set(got)
+    assert seen == set(want)  # every recorded array was compared

@@ -14,7 +14,7 @@ LDS="SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_SALU SQ_INSTS_SME
 MFMA="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVE_CYCLES GRBM_GUI_ACTIVE GRBM_COUNT"
 for cfg in cfg2_resnet50_r1 cfg3_resnet50_r4; do
   mkdir -p "$out/$cfg"
-  B="bench.py --config $cfg --steps 20 --warmup 3 --mode cold --no-cpu-baseline --no-extra"
+  B="bench.py --config $cfg --steps 20 --warmup 3 --mode cold --full --no-cpu-baseline --no-extra"
   timeout -s KILL 120 rocprofv3 --pmc $STALL --output-format csv -d "$out/$cfg/stall" -o stall -- python3 $B > "$out/$cfg/stall.log" 2>&1
   if grep -q -w SQ_INSTS_LDS "$out/counters_list.txt" && grep -q -w SQ_INSTS_VMEM_RD "$out/counters_list.txt"; then
     timeout -s KILL 120 rocprofv3 --pmc $LDS --output-format csv -d "$out/$cfg/lds" -o lds -- python3 $B > "$out/$cfg/lds.log" 2>&1 || echo "lds pass failed ($cfg)"

@@ -12,7 +12,7 @@ sys.path.insert(0, ".")
 import bench  # noqa: E402
 
 a = argparse.Namespace(steps=int(os.environ.get("AB_STEPS", "100")), warmup=10, sets=4, iters=None,
-                       config="cfg3_resnet50_r4")
+                       config="cfg3_resnet50_r4", full=True)  # full: the block carries its roofline pass
 dev = torch.device("cuda:0")
 torch.cuda.set_device(dev)
 r = bench.one_rank_group(a, dev)

@@ -1,5 +1,5 @@
 // RCCL inside libpsgd: communicators and the stream-ordered SUM all-reduce of a world-size-W
-// step (psgd_aggregate_comm, psgd_plan.cpp). RCCL is resolved at run time with dlopen/dlsym
+// step (psgd_aggregate_comm, psgd_step.cpp). RCCL is resolved at run time with dlopen/dlsym
 // (psgd_comm_* in include/psgd.h): an RCCL the process has already loaded (PyTorch's) is reused,
 // else PSGD_RCCL_LIB or the ROCm one; the library has no link-time dependency on it.
 // PSGD_RCCL_LIB_FORCE=<path> (tests only) takes precedence over all of these and is read at

@@ -1,4 +1,4 @@
-// Internal layout shared by the host plan (psgd_plan.cpp) and the HIP kernels.
+// Internal layout shared by the host units (psgd_plan.h) and the HIP kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,0 +1,429 @@
+// Host-side definitions shared by the units behind the C ABI of include/psgd.h:
+//   psgd_geometry.cpp  tile geometry, segmentation, work-list capacities and the workspace carve
+//   psgd_plan.cpp      plan lifecycle: create, queries, bind, buckets, timing
+//   psgd_step.cpp      step drivers and the reducer building blocks
+//   psgd_ipc.cpp       the IPC exchange arena and psgd_aggregate_ipc
+//   psgd_flat.cpp      flat pack and DDP run tables
+// No torch: plain pointers, hipStream_t as void*. Never included by device code.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "psgd.h"
+#include "psgd_internal.h"
+
+namespace psgd {
+
+// per-dtype kernel launchers (psgd_*_f32.hip / psgd_*_bf16.hip) and their dtype dispatch
+#define PSGD_PER_DTYPE(ret, fn, ...) \
+    ret fn##_f32(__VA_ARGS__);       \
+    ret fn##_bf16(__VA_ARGS__);
+PSGD_PER_DTYPE(hipError_t, launch_even, int R, int nres, const ProductArgs& a, int nwg, hipStream_t s)
+PSGD_PER_DTYPE(int, even_resident, int R)
+PSGD_PER_DTYPE(hipError_t, launch_product_odd, int R, int nres, const ProductArgs& a, int ntiles, hipStream_t s)
+PSGD_PER_DTYPE(hipError_t, launch_apply, int R, int nterms, bool shared, const ApplyArgs& a, int ntiles, hipStream_t s)
+PSGD_PER_DTYPE(hipError_t, launch_odd_mfma, int R, int nres, const ProductArgs& a, int ntiles, hipStream_t s)
+PSGD_PER_DTYPE(hipError_t, launch_final_odd, int R, int nres, int smax, const FinalArgs& a, int ntiles, hipStream_t s,
+               int* waves)
+PSGD_PER_DTYPE(hipError_t, launch_lowrank_out, int R, int nterms, const ApplyArgs& a, int ntiles, hipStream_t s)
+PSGD_PER_DTYPE(hipError_t, launch_final_oe, int nres, int smax, const FinalArgs& a, int ntiles, hipStream_t s, int* waves)
+#undef PSGD_PER_DTYPE
+hipError_t launch_even(int dtype, int R, int nres, const ProductArgs& a, int nwg, hipStream_t s);
+hipError_t launch_product_odd(int dtype, int R, int nres, const ProductArgs& a, int ntiles, hipStream_t s);
+
+// records the message for psgd_last_error and returns `code`
+int fail(int code, const std::string& msg);
+
+#define PSGD_HIP(expr)                                                                   \
+    do {                                                                                 \
+        const hipError_t e_ = (expr);                                                    \
+        if (e_ != hipSuccess)                                                            \
+            return fail(PSGD_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+inline int64_t pow2ceil(int64_t x) {
+    int64_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
+inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+int64_t env_int(const char* name, int64_t dflt);
+int upload(void* dst, const void* src, size_t bytes);  // synchronous host-to-device copy
+
+// One device work list: the host vector (the list is used as one), its capacity in elements and
+// its byte offset in the caller's workspace. carve() places it once at create; every upload()
+// checks the capacity, so a re-tiling of a bound plan can never write past the list's region.
+template <typename T>
+struct DevList : std::vector<T> {
+    const char* name;
+    size_t cap = 0, off = 0;
+    explicit DevList(const char* n) : name(n) {}
+    void carve(size_t& ws_off, size_t capacity) {
+        off = ws_off;
+        cap = capacity;
+        ws_off = align256(ws_off + cap * sizeof(T));
+    }
+    T* dev(char* ws) const { return reinterpret_cast<T*>(ws + off); }
+    int upload(char* ws) const {
+        if (this->size() > cap)
+            return fail(PSGD_ERR_STATE, std::string("work list ") + name + " exceeds its workspace capacity");
+        return psgd::upload(ws + off, this->data(), this->size() * sizeof(T));
+    }
+};
+template <typename... L>
+int upload_all(char* ws, const L&... lists) {  // stops at the first failure
+    int st = PSGD_OK;
+    ((st = st ? st : lists.upload(ws)), ...);
+    return st;
+}
+
+// Device-resident pointer tables (gradients, destinations) without a host synchronisation.
+// kSlots tables live in the caller's workspace; a call whose pointer set matches a slot uses
+// it as is (callers that rotate a few gradient sets, or get fresh tensors from the caching
+// allocator, hit after the first round). A miss takes the least recently used slot and
+// uploads into it with hipMemcpyAsync ON THE LAUNCH STREAM from a pinned staging copy, so
+// the copy is ordered after every earlier launch on that stream that may still read the
+// slot, and the host never waits (the reference hands tensors to torch ops, which never
+// synchronise either). Calls of one plan must be ordered on one stream (as torch's are).
+struct TableCache {
+    static constexpr int kSlots = 4;
+    size_t n = 0;              // pointers per table
+    char* dev = nullptr;       // kSlots * n pointers inside the workspace
+    std::vector<void*> host[kSlots];
+    uint64_t stamp[kSlots] = {};
+    uint64_t clock = 0;
+    int cur = -1;
+    void** pinned = nullptr;   // kSlots * n staging pointers (hipHostMalloc)
+    hipEvent_t ev[kSlots] = {};
+    bool live[kSlots] = {};
+
+    static size_t bytes(size_t n) { return size_t(kSlots) * std::max<size_t>(n, 1) * sizeof(void*); }
+    void bind(char* d, size_t count) {
+        release();
+        dev = d;
+        n = count;
+        for (auto& h : host) h.clear();
+        cur = -1;
+    }
+    void release() {
+        for (int i = 0; i < kSlots; ++i) {
+            if (live[i]) (void)hipEventSynchronize(ev[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+            ev[i] = nullptr;
+            live[i] = false;
+        }
+        if (pinned) (void)hipHostFree(pinned);
+        pinned = nullptr;
+    }
+    ~TableCache() { release(); }
+    bool match(int i, void* const* p) const { return host[i].size() == n && std::equal(p, p + n, host[i].begin()); }
+    // 0 on success, else a hipError_t
+    hipError_t select(void* const* p, hipStream_t s) {
+        ++clock;
+        if (cur >= 0 && match(cur, p)) {
+            stamp[cur] = clock;
+            return hipSuccess;
+        }
+        int victim = 0;
+        for (int i = 0; i < kSlots; ++i) {
+            if (match(i, p)) {
+                cur = i;
+                stamp[i] = clock;
+                return hipSuccess;
+            }
+            if (stamp[i] < stamp[victim]) victim = i;
+        }
+        if (!pinned) {
+            hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&pinned), bytes(n), hipHostMallocDefault);
+            if (e != hipSuccess) {
+                pinned = nullptr;
+                return e;
+            }
+            for (int i = 0; i < kSlots; ++i)
+                if ((e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)) != hipSuccess) return e;
+        }
+        // the staging slot may still feed the previous upload into this slot
+        if (live[victim]) {
+            const hipError_t e = hipEventSynchronize(ev[victim]);
+            if (e != hipSuccess) return e;
+        }
+        void** stage = pinned + size_t(victim) * n;
+        std::copy(p, p + n, stage);
+        hipError_t e = hipMemcpyAsync(dev + size_t(victim) * n * sizeof(void*), stage, n * sizeof(void*),
+                                      hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipEventRecord(ev[victim], s);
+        if (e != hipSuccess) return e;
+        live[victim] = true;
+        host[victim].assign(p, p + n);
+        stamp[victim] = clock;
+        cur = victim;
+        return hipSuccess;
+    }
+    void* const* table() const { return reinterpret_cast<void* const*>(dev + size_t(cur) * n * sizeof(void*)); }
+};
+
+struct DevScope {  // make `dev` current for the scope, restore afterwards
+    int prev = -1;
+    explicit DevScope(int dev) {
+        (void)hipGetDevice(&prev);
+        if (dev >= 0 && dev != prev) (void)hipSetDevice(dev);
+    }
+    ~DevScope() {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+// Persistent even product (k_even): workgroups per launch (CUs x workgroups per CU), at least
+// even_min gradient elements per workgroup (small plans use fewer, fuller workgroups), at
+// most kMaxBuckets buckets (each bucket launch spreads over the whole chip).
+constexpr int kCUs = 256;                // MI355X
+constexpr int kEvenWpcMax = 16;          // k_even workgroups per CU (PSGD_EVEN_WPC cap)
+constexpr int kEvenWgMax = kEvenWpcMax * kCUs;  // workgroups per launch (capacity)
+constexpr int kMaxBuckets = 8;
+
+int fin_bucket(int s);  // kernel instance (segments per row) serving s segments; 0: none
+
+}  // namespace psgd
+
+using namespace psgd;  // the opaque C types below are global (include/psgd.h)
+
+struct psgd_plan {
+    int rank = 0, iters = 0, dtype = 0;
+    std::vector<std::vector<int64_t>> shapes;
+    struct Group {
+        int64_t n, m;
+        int r;
+        std::vector<int> tensors;
+        int64_t poff, qoff;
+    };
+    std::vector<Group> groups;
+    DevList<MatDesc> mats{"mats"};  // group order
+    std::vector<int> base_vec;  // vector path possible by shape (m % 4 == 0, r <= 8)
+    std::vector<int> vec_now;   // currently active vector flags
+    std::vector<int64_t> out_off;
+    int64_t out_total = 0, ptot = 0, qtot = 0, fmax = 0;
+    int rbucket = 1;
+    int64_t tile_elems = 16384;
+    DevList<Tile> tiles{"tiles"};        // lane-column tiles of every matrix (apply, low-rank output)
+    DevList<Tile> tiles_ov{"tiles_ov"};  // lane-column tiles of the odd-VALU matrices
+    DevList<Tile> tiles_om{"tiles_om"};  // MFMA tiles of the odd-MFMA matrices
+    DevList<Tile> tiles_fin{"tiles_fin"};  // row blocks of the fused final odd pass
+    // the K-term form's own row blocks when they differ from the projection form's (MatDesc::
+    // fin_rows_kt); empty: the K-term form uses tiles_fin
+    DevList<Tile> tiles_fin_kt{"tiles_fin_kt"};
+    // environment knobs, read once at create: PSGD_FUSE_FINAL, PSGD_FIN_PROJ, PSGD_OE (0: that
+    // fused form is never used), PSGD_ORTH_CHOL (Cholesky-QR vs Householder)
+    bool fuse_final_on = true, fin_proj_on = true, oe_on = true, orth_chol = true;
+    bool fin_ok = false;         // every matrix fits the fused final odd pass (K-term form)
+    bool fin_proj = false;       // ... in its projection form (I = 2, psgd_aggregate only)
+    int fin_smax = 0;
+    int64_t fin_elems = 32768, fin_elems_kt = 32768;
+    // output stores of the fused final pass nt only (psgd_stream.cuh kStAuxOutNt): plans whose
+    // gradients exceed 32 MB; smaller plans keep the write-through policy
+    int32_t out_nt = 0;
+    // even product (k_even): segments, per-workgroup segment ranges (wg_seg[w] .. wg_seg[w+1]),
+    // workgroups per CU and the minimum elements per workgroup (read at create)
+    DevList<Seg> segs{"segs"};
+    DevList<int32_t> wg_seg{"wg_seg"};
+    int even_wpc = 4;
+    int64_t even_segc = 4096;  // k_even cost model: elements-equivalent of one segment's fixed cost
+    int64_t even_min = 16384;
+    // odd-even pass (k_final_oe: rank 1, world size 1, I >= 3): an odd iteration followed by an
+    // even one inside a step in ONE gradient pass; its partials (per K-term row block, [m]) are
+    // summed by k_reduce over red_oe, the blocks' sums of P^2 (oe_ss) give the even iteration's
+    // joint norm (grng_oe: per group its block range), and the items' sums of squares feed the
+    // next fused iteration (grng_oe_items: per group its red_oe range)
+    bool oe_ok = false;
+    DevList<RedItem> red_oe{"red_oe"};
+    DevList<Tile> tiles_oe{"tiles_oe"};  // its row blocks (MatDesc::oe_rows rows)
+    DevList<int32_t> grng_oe{"grng_oe"}, grng_oe_items{"grng_oe_items"};
+    int64_t oe_part_floats = 0;
+    int32_t oe_blocks = 0;
+    bool oe_at(int64_t step, int it, bool agg) const {  // iteration `it` runs the odd-even pass
+        return oe_ok && agg && it >= 1 && it + 1 < iters && !even(step, it);
+    }
+    // reduction items (rebuilt with the geometry): even items follow the segmentation
+    DevList<RedItem> red_even{"red_even"}, red_odd{"red_odd"};
+    // per group: [begin, end) of its reduction items
+    DevList<int32_t> grng_even{"grng_even"}, grng_odd{"grng_odd"};
+    DevList<OrthUnit> units_p{"units_p"}, units_q{"units_q"};
+    // one unit per MATRIX (paper-code Gram-Schmidt)
+    DevList<OrthUnit> munits_p{"munits_p"}, munits_q{"munits_q"};
+    TableCache grad_tab, rdst_tab, odst_tab;  // device pointer tables (gradients, destinations)
+    int64_t panel_p = 0, panel_q = 0;
+    int64_t part_odd_floats = 0;  // odd partials [odd strips][n][r] per matrix; even ones follow
+    double unc_floats = 0, comp_floats = 0;
+    // Scratch regions of the workspace that mirror no host list (byte offsets): the pointer
+    // tables of the three TableCaches, factor history, product partials, sums of squares (two
+    // parities of ss_stride floats; the iteration-0 fold's ss0_cap slots), the folded
+    // orthonormalisation's Gram partials, R' of the last iteration's in-factor panels
+    // (projection form, Q layout), the odd-even pass's partials and sums, the fp64 partials
+    size_t o_ptrs = 0, o_rdst = 0, o_odst = 0, o_hist = 0, o_part = 0, o_ss = 0, ss_stride = 0, o_ss0 = 0,
+           o_gram = 0, o_rq = 0, o_oe_part = 0, o_oe_ss = 0, o_f64_part = 0, ws_bytes = 0;
+    int64_t ss0_cap = 0;
+    // rank-1 iteration-0 norm fold: per strip-0 segment a sum-of-squares slot, and per group the
+    // [begin, end) slot range
+    DevList<int32_t> grng_ss0{"grng_ss0"};
+    // Buckets of whole shape groups (W > 1 overlap, psgd_plan_set_buckets): per bucket the
+    // [begin, end) range of every launch list (all are in matrix order) and of the P/Q buffers.
+    struct Span {
+        int32_t tiles[2], ov[2], om[2], fin[2], fin_kt[2], re[2], ro[2], up[2], uq[2], wg[2];
+        int64_t p[2], q[2];
+    };
+    std::vector<int32_t> bucket_gend;              // exclusive group end per bucket
+    std::vector<int32_t> bucket_wg;                // per bucket [begin, end) of its k_even workgroups
+    std::vector<Span> spans;
+    std::vector<int32_t> unit_group_p, unit_group_q;
+    Span full_span() const;
+    void build_spans();
+
+    // fp64 plans (psgd_f64.hip): even tiles (64-column strip, 256-row chunk), odd tiles
+    // (16-row blocks), apply tiles (row chunks of ~16k elements), even partial offsets
+    DevList<Tile> f64_even{"f64_even"}, f64_odd{"f64_odd"}, f64_apply{"f64_apply"};
+    DevList<int64_t> f64_part_off{"f64_part_off"};
+    int64_t f64_part = 0;
+    bool bound = false;
+    int device = -1;
+    float* P = nullptr;
+    float* Q = nullptr;
+    char* ws = nullptr;
+    // benchmark timing of the final pass: event pairs recorded on the launch stream
+    bool timing = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    size_t ev_used = 0;
+    // one-shot IPC all-reduce (psgd_ipc_*, psgd_aggregate_ipc): this rank's exchange buffer
+    // (flags header + 2 parities x iters slots), the peers' opened mappings and session nonces,
+    // the slot size (floats: factor region, then the flat region)
+    char* ipc_buf = nullptr;      // this session's region of the process's exchange arena
+    int ipc_chunk = -1;           // the region: arena chunk, byte offset and size
+    size_t ipc_off = 0, ipc_bytes = 0;
+    DevList<void*> ipc_peer{"ipc_peer"};
+    DevList<uint32_t> ipc_nonces{"ipc_nonces"};
+    int ipc_world = 0, ipc_rank = -1;
+    int64_t ipc_slot = 0, ipc_flat_off = 0, ipc_flat_cap = 0;
+    uint32_t ipc_nonce = 0;  // this rank's exchange session (psgd_ipc_create)
+    // sticky timeout word of the exchange waits: pinned host memory mapped into the device
+    // (k_xchg stores 1 with a system-scope store), so every psgd_aggregate_ipc call can check it
+    // without synchronising; cleared only by psgd_ipc_close
+    int32_t* xerr_host = nullptr;
+    int32_t* xerr_dev = nullptr;
+    bool xerr_set() const { return xerr_host && __atomic_load_n(xerr_host, __ATOMIC_ACQUIRE) != 0; }
+    unsigned long long* stamp_buf = nullptr;  // diagnostic k_even stamps (PSGD_EVEN_STAMPS)
+    size_t stamp_words = 0;
+    int64_t xslot_off(int64_t step, int it) const {  // byte offset of a slot in every buffer
+        return kXchgHeader + ((step & 1) * iters + it) * ipc_slot * int64_t(sizeof(float));
+    }
+    float* xslot(int64_t step, int it) const { return reinterpret_cast<float*>(ipc_buf + xslot_off(step, it)); }
+    // folded orthonormalisation of the projection form's Q panels (k_orth_chain): every Q unit
+    // a single panel of exactly rbucket in {2, 4} columns; per-item Gram partials and per-unit
+    // item ranges
+    bool qfold_ok = false;
+    DevList<int32_t> uitems{"uitems"};
+    std::vector<int32_t> red_even_b, red_even_e;
+    DevList<int32_t> mrng_even{"mrng_even"};  // per matrix [begin, end) of its even reduction items
+    bool qfold(int64_t step, bool agg) const { return qfold_ok && iters == 2 && proj_final(step, agg); }
+
+    ~psgd_plan();
+
+    float* hist(int which, int k) const {  // 0: X (orthonormal in-factor), 1: Y local, 2: Y reduced
+        return reinterpret_cast<float*>(ws + o_hist) + (int64_t(which) * iters + k) * fmax;
+    }
+    double* hist64(int which, int k) const {  // the same history, fp64 plans
+        return reinterpret_cast<double*>(ws + o_hist) + (int64_t(which) * iters + k) * fmax;
+    }
+    bool f64() const { return dtype == PSGD_F64; }
+    template <typename T>
+    T* dev(size_t off) const { return reinterpret_cast<T*>(ws + off); }
+    template <typename T>
+    T* dev(const DevList<T>& l) const { return l.dev(ws); }
+    bool even(int64_t step, int it) const { return ((step * iters + it) % 2) == 0; }
+
+    // psgd_geometry.cpp
+    void set_f64_tiles();
+    void build_reduction();
+    void set_vec(const std::vector<int>& vec);
+    void build_oe();
+    void layout(int num_tensors);  // capacities, first tiling, workspace carve (once, at create)
+    int upload_tiles() const;      // every list set_vec / set_f64_tiles rebuilds
+
+    // the last iteration of `step` runs fused (odd, and every matrix fits); `agg`: the caller
+    // is psgd_aggregate (world size 1, output written), where the projection form also applies
+    bool fused_final(int64_t step, bool agg) const { return (fin_ok || (agg && fin_proj)) && !even(step, iters - 1); }
+    // the fused last iteration takes the projection form
+    bool proj_final(int64_t step, bool agg) const { return agg && fin_proj && !even(step, iters - 1); }
+    bool fused_final_at(int64_t step, int it, bool agg) const { return it == iters - 1 && fused_final(step, agg); }
+    // Every group rank 1, iteration >= 1, a caller that folds (`fuse`: psgd_aggregate and the
+    // IPC exchange): the joint-norm orthonormalisation of the in-factor is folded into the
+    // neighbouring reductions (no orthonormalisation launch): the previous reduction leaves
+    // per-item sums of squares, the product runs on the raw in-factor, and this iteration's
+    // reduction divides by the norm and writes the normalised in-factor (reference
+    // powersgd.py:186-188 + orthogonalization.py:5-6).
+    bool fused_norm(bool fuse, int it) const { return fuse && rbucket == 1 && it >= 1; }
+};
+
+struct psgd_flat {
+    int dtype = 0;
+    DevList<FlatEntry> entries{"flat entries"};  // non-empty tensors only
+    DevList<FlatItem> items{"flat items"};
+    int32_t count = 0;
+    int64_t total = 0;
+    size_t o_ptrs = 0, ws_bytes = 0;
+    bool bound = false;
+    int device = -1;
+    char* ws = nullptr;
+    TableCache tab;  // device pointer tables of the tensors
+};
+
+// DDP bucket <-> parameter tensors (psgd_runs_*, include/psgd.h): the work items of one run
+// table and the device pointer tables of the tensors it addresses
+struct psgd_runs {
+    int dtype = 0;
+    int32_t ntensors = 0;
+    DevList<RunItem> items{"run items"};
+    int64_t bucket_numel = 0;  // one past the last bucket element any run touches
+    size_t o_ptrs = 0, ws_bytes = 0;
+    bool bound = false;
+    int device = -1;
+    char* ws = nullptr;
+    TableCache tab;
+};
+
+namespace psgd {
+
+// What one call of a step driver passes down to compress_impl / decompress_impl: built on the
+// entry point's stack, never stored in the plan.
+struct StepCtx {
+    bool fuse = false;       // fold the rank-1 joint norm into the kernels (psgd_plan::fused_norm)
+    bool write_out = false;  // psgd_aggregate at world size 1: the fused final pass writes `out`
+    const FlatArgs* fl = nullptr;            // uncompressed tensors riding in a launch
+    const psgd_plan::Span* span = nullptr;   // one bucket's ranges; null: the whole plan
+    void* out = nullptr;     // psgd_aggregate's output buffer (fused final pass)
+    float* xout = nullptr;   // psgd_aggregate_ipc: this iteration's exchange slot
+    // history slot of the RAW in-factor the rank-1 norm fold reads: 1 (the local reduction's
+    // output, world size 1) or 2 (the exchange's summed copy, psgd_aggregate_ipc)
+    int raw_slot = 1;
+    // psgd_aggregate_ipc, ranks 2/4, two iterations: the exchange of iteration 0 left the summed
+    // Q panels' Gram partials, so iteration 1 orthonormalises with k_orth_chain
+    bool xgram = false;
+};
+
+// psgd_step.cpp
+int refresh_pointers(psgd_plan* p, void* const* grads, hipStream_t stream);
+int compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s, StepCtx c);
+int decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s,
+                    StepCtx c);
+// psgd_flat.cpp: device-side arguments of a flat pack (selects or uploads the pointer table)
+int flat_args(psgd_flat* f, void* const* tensors, void* flat, int32_t world, hipStream_t s, FlatArgs* out);
+// psgd_ipc.cpp: the plan's exchange region goes back to the process's arena
+void ipc_release(psgd_plan* p);
+
+}  // namespace psgd

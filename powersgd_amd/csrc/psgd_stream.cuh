@@ -1248,7 +1248,7 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
     __syncthreads();  // qs is staged again by the next tile of this workgroup (none today)
 }
 
-// ONT: the output stores nt only (world size 1, plans above PSGD_OUT_NT_MB: the averaged
+// ONT: the output stores nt only (world size 1, plans above 32 MB of gradients: the averaged
 // gradient the optimizer reads next does not sit dirty in the Infinity Cache ahead of the next
 // step's cold reads); a compile-time instance, so the store form costs no registers
 template <typename T, int R, int NI, bool SHARED, bool ONT = false>

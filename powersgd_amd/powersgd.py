@@ -383,8 +383,11 @@ class BasicPowerSGD(Aggregator):
 
     def close(self) -> None:
         """Release the multi-GPU transports (collective: every rank calls it). The exchange
-        buffers of PSGD_COMM=ipc are unmapped and the ranks meet at a barrier before any frees
-        its buffer; without this call an exit hook does the same with a bounded barrier."""
+        session of PSGD_COMM=ipc is closed and the ranks meet at a barrier, so that no peer kernel
+        still reads a region when a later session re-zeroes it. The region itself goes back to the
+        process's exchange arena: arena chunks are never freed and peer mappings never unmapped
+        until the process exits. Without this call an exit hook does the same with a bounded
+        barrier."""
         self.close_ipc()
         self._comm = None
 

@@ -1,4 +1,4 @@
-"""The odd-even pass (k_final_oe, psgd_plan.cpp oe_at): at rank 1, world size 1 and num_iters_per_step
+"""The odd-even pass (k_final_oe, psgd_plan.h oe_at): at rank 1, world size 1 and num_iters_per_step
 >= 3, an odd power iteration followed by an even one (reference powersgd.py:172-202 twice: P_k =
 G_k X_k, G_{k+1} = G_k - P_k X_k^T, Q_{k+1} = G_{k+1}^T orth(P_k)) runs as ONE gradient pass: the
 row pass that forms P_k also accumulates the next product's column partials on the raw P_k, and

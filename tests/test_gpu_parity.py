@@ -230,9 +230,9 @@ def test_orthonormal_in_factor_every_rank_bucket(rank):
 
 @pytest.mark.parametrize("rank,iters", [(12, 2), (16, 2), (16, 3), (32, 2)])
 def test_wide_rank_free_running(rank, iters):
-    """Ranks 9-32: k_orth_chol16/32 (fp64 MFMA Cholesky-QR) and k_apply with register-cached
-    terms (I = 2) or per-element factor loads (I = 3), two free-running steps with error
-    feedback against the oracle from the same initial state."""
+    """Ranks 9-32: k_orth_chol16/32 (fp64 MFMA Cholesky-QR) and k_apply's matrix-core tiles
+    (apply_tile_mfma, any term count; its fallback loads factor rows per element where m % 4 != 0),
+    two free-running steps with error feedback against the oracle from the same initial state."""
     shapes = [(300, 200), (64, 1000), (1000, 64), (128, 8, 3, 3), (40,)]
     params = [torch.zeros(s, device=DEV) for s in shapes]
     psgd = PowerSGD(params, Config(rank, 0.1, iters, 0))

@@ -68,7 +68,7 @@ def test_rccl_step_one_rank_vs_oracle(cfg, tmp_path):
 
 
 def test_rccl_kterm_own_row_blocks_vs_oracle(tmp_path):
-    """The K-term final pass on its own row blocks (psgd_plan.cpp tiles_fin_kt, MatDesc::
+    """The K-term final pass on its own row blocks (psgd_plan.h tiles_fin_kt, MatDesc::
     fin_rows_kt) at an odd block size, 5000 elements: ragged against every ResNet-50 row length,
     beside the projection form's default blocks of the same plan."""
     torch.multiprocessing.spawn(_worker, args=(str(tmp_path / "init"), "cfg2_resnet50_r1", 2,

@@ -1,4 +1,4 @@
-"""The library's RCCL orchestration (psgd_aggregate_comm, psgd_plan.cpp) at world size W > 1 on ONE
+"""The library's RCCL orchestration (psgd_aggregate_comm, psgd_step.cpp) at world size W > 1 on ONE
 GPU, through a stand-in collective library (tests/stubs/rccl_stub.hip, loaded with
 PSGD_RCCL_LIB_FORCE): its communicator reports world W and its SUM all-reduce writes W x the
 buffer, which is exactly the SUM over W ranks holding identical gradients. The result must match

@@ -38,6 +38,14 @@
  *    :241-251 allocates them in the default dtype, which must match the gradients' for its bmm).
  *  - The building blocks (psgd_product / psgd_orthogonalize / psgd_reconstruct) and the fused
  *    fp32 kernels take fp32/bf16 plans only (PSGD_ERR_DTYPE for an F64 plan).
+ *  - Rank limit: the effective rank min(rank, n, m) of every matrix is at most 128 for
+ *    fp32/bf16 plans and at most 32 for fp64 plans (PSGD_ERR_VALUE at psgd_plan_create). A plan
+ *    whose largest effective rank exceeds 32 is a WIDE plan (psgd_plan_is_wide): same P/Q layout,
+ *    its own matrix-core kernels, none of the fused forms. psgd_compress, psgd_decompress,
+ *    psgd_aggregate, psgd_aggregate_flat, psgd_aggregate_comm, the timing calls and every
+ *    psgd_plan_* query take wide plans; psgd_plan_set_buckets with more than one bucket, the
+ *    *_bucket calls, the building blocks and psgd_ipc_create refuse them (PSGD_ERR_VALUE,
+ *    nothing is launched).
  *  - Errors: every call returns a psgd_status; psgd_last_error() returns a thread-local message.
  *    PSGD_ERR_INDEX mirrors the reference's IndexError (no tensors, :118), PSGD_ERR_DTYPE its
  *    RuntimeError on unsupported dtypes (:189), PSGD_ERR_LAYOUT its RuntimeError on
@@ -94,7 +102,8 @@ int psgd_should_compress(const int64_t* shape, int32_t ndim, int32_t rank,
  * (ndims[i] entries each). Matrices are the view [shape[0], numel/shape[0]]; they are
  * grouped by matrix shape in first-appearance order, and the P (resp. Q) state buffer
  * is the concatenation over groups of [count, n, r] (resp. [count, m, r]) fp32 arrays,
- * r = min(rank, n, m) — byte-for-byte the reference's _ps_buffer/_qs_buffer layout. */
+ * r = min(rank, n, m) — byte-for-byte the reference's _ps_buffer/_qs_buffer layout.
+ * The largest r may be 128 (fp32 / bf16) or 32 (fp64); beyond that PSGD_ERR_VALUE. */
 int psgd_plan_create(const int64_t* dims, const int32_t* ndims, int32_t num_tensors,
                      int32_t rank, int32_t num_iters_per_step, int32_t dtype,
                      psgd_plan** out_plan);
@@ -226,6 +235,9 @@ int psgd_plan_fused_final(const psgd_plan* plan, int64_t step, int32_t aggregate
 /* Nonzero when iteration `it` of `step` (odd, followed by an even one) runs as ONE gradient pass
  * with the next iteration's product inside psgd_aggregate (rank 1, world size 1, I >= 3). */
 int psgd_plan_odd_even(const psgd_plan* plan, int64_t step, int32_t it, int32_t* on);
+/* 1 when the plan's largest effective rank exceeds 32 (rank bucket 64 or 128): the wide-rank
+ * path. psgd_plan_fused_final and psgd_plan_odd_even report 0 for such a plan. */
+int psgd_plan_is_wide(const psgd_plan* plan, int32_t* out);
 
 /* Kernel timing for benchmarks: when enabled, every final pass launched by psgd_aggregate
  * (k_apply, or the fused final odd kernel) and by psgd_decompress (k_apply) is bracketed by HIP events recorded on its own stream.

@@ -39,6 +39,7 @@ _SIGNATURES = {
     "psgd_aggregate": ([_vp, _vp, _vp, _i64, _vp], _i32),
     "psgd_plan_fused_final": ([_vp, _i64, _i32, _P_i32], _i32),
     "psgd_plan_odd_even": ([_vp, _i64, _i32, _P_i32], _i32),
+    "psgd_plan_is_wide": ([_vp, _P_i32], _i32),
     "psgd_plan_set_timing": ([_vp, _i32], _i32),
     "psgd_plan_timing_read": ([_vp, _P_dbl, _P_i32], _i32),
     "psgd_flat_create": ([_P_i64, _i32, _i32, ctypes.POINTER(_vp)], _i32),
@@ -277,6 +278,13 @@ class Plan:
         product in one gradient pass (psgd_aggregate: rank 1, world size 1, I >= 3)."""
         f = _i32()
         check(lib().psgd_plan_odd_even(self._h, step, it, ctypes.byref(f)))
+        return bool(f.value)
+
+    def is_wide(self) -> bool:
+        """True when the plan's largest effective rank exceeds 32 (the wide-rank path: ranks up to
+        128, fp32 / bf16; no buckets, IPC exchange or building blocks)."""
+        f = _i32()
+        check(lib().psgd_plan_is_wide(self._h, ctypes.byref(f)))
         return bool(f.value)
 
     # --- building blocks (paper-code reducer variants, powersgd_amd/reducers.py)

@@ -178,6 +178,75 @@ void psgd_plan::set_f64_tiles() {
     }
 }
 
+// Wide plans (psgd_wide.hip). A product workgroup owns kWideOut out-factor rows (matrix columns
+// for the even product, matrix rows for the odd one) and sums over one chunk of the other
+// dimension; a matrix is cut into about 1024 / (its out blocks) chunks of at least 512, so a
+// plan of one large matrix still fills the chip and the partials stay under a quarter of the
+// gradient traffic at rank 128. Partials [chunks][out rows][r] are summed in chunk order.
+void psgd_plan::set_wide_tiles() {
+    wide_even.clear();
+    wide_odd.clear();
+    wide_apply.clear();
+    wide_part = 0;
+    vec_now = base_vec;
+    red_even.clear();
+    red_odd.clear();
+    // orthonormalisation: row blocks of every rank > 1 panel (rank-1 units have no Gram)
+    wide_slots = 0;
+    for (int side = 0; side < 2; ++side) {
+        const DevList<OrthUnit>& units = side ? units_q : units_p;
+        DevList<Tile>& items = side ? wide_gq : wide_gp;
+        DevList<int32_t>& slot0 = side ? wide_slot_q : wide_slot_p;
+        items.clear();
+        slot0.clear();
+        int32_t slot = 0;
+        for (size_t ui = 0; ui < units.size(); ++ui) {
+            slot0.push_back(slot);
+            if (units[ui].r == 1) continue;
+            for (int64_t b = 0; b * kWideGramRows < units[ui].k; ++b) items.push_back(Tile{int32_t(ui), int32_t(b), slot++, 0});
+        }
+        wide_slots = std::max<int64_t>(wide_slots, slot);
+    }
+    auto chunk_of = [](int64_t out_len, int64_t sum_len) {
+        const int64_t nout = (out_len + kWideOut - 1) / kWideOut;
+        const int64_t want = std::max<int64_t>(1, 1024 / nout);
+        const int64_t nch = std::max<int64_t>(1, std::min(want, (sum_len + 511) / 512));
+        return round_up((sum_len + nch - 1) / nch, kWideStep);
+    };
+    for (size_t i = 0; i < mats.size(); ++i) {
+        MatDesc& d = mats[i];
+        d.vec = 0;
+        // even: out = columns, summed over row chunks
+        d.nstrip = int32_t((d.m + kWideOut - 1) / kWideOut);
+        d.chunk_rows = int32_t(chunk_of(d.m, d.n));
+        d.nchunk = int32_t((d.n + d.chunk_rows - 1) / d.chunk_rows);
+        d.part_even = wide_part;
+        wide_part += int64_t(d.nchunk) * d.m * d.r;
+        // odd: out = rows, summed over column strips
+        d.odd_mfma = 1;
+        d.odd_chunk_rows = kWideOut;
+        d.odd_sw = int32_t(chunk_of(d.n, d.m));
+        d.odd_nstrip = int32_t((d.m + d.odd_sw - 1) / d.odd_sw);
+        d.part_odd = wide_part;
+        wide_part += int64_t(d.odd_nstrip) * d.n * d.r;
+        const int32_t nrb = int32_t((d.n + kWideOut - 1) / kWideOut);
+        for (int c = 0; c < d.nchunk; ++c)
+            for (int st = 0; st < d.nstrip; ++st) wide_even.push_back(Tile{int32_t(i), st, c, d.tensor});
+        for (int b = 0; b < nrb; ++b)
+            for (int st = 0; st < d.odd_nstrip; ++st) wide_odd.push_back(Tile{int32_t(i), st, b, d.tensor});
+        for (int b = 0; b < nrb; ++b)
+            for (int64_t st = 0; st * kWideApplyCols < d.m; ++st)
+                wide_apply.push_back(Tile{int32_t(i), int32_t(st), b, d.tensor});
+        // k_wide_reduce: kRedItem consecutive factor elements per item
+        for (int64_t s = 0; s < d.m * d.r; s += kRedItem)
+            red_even.push_back(RedItem{int32_t(i), int32_t(s), 1, int32_t(std::min<int64_t>(kRedItem, d.m * d.r - s)), 0, 0,
+                                       d.nchunk});
+        for (int64_t s = 0; s < d.n * d.r; s += kRedItem)
+            red_odd.push_back(RedItem{int32_t(i), int32_t(s), 1, int32_t(std::min<int64_t>(kRedItem, d.n * d.r - s)), 0, 0,
+                                      d.odd_nstrip});
+    }
+}
+
 // Even-product segmentation (k_even) and every reduction item list, for the current strip
 // geometry and buckets. Per bucket (or the whole plan), the gradient elements of its
 // matrices (walked matrix -> strip -> row) are cut into nwg equal ranges, one per workgroup;
@@ -574,6 +643,10 @@ void psgd_plan::layout(int num_tensors) {
     if (f64()) {
         set_f64_tiles();  // fp64: its own kernels and tiles (psgd_f64.hip), no fused forms
         red_even_cap = std::max<int64_t>(red_even_cap, int64_t(red_even.size()));
+    } else if (wide()) {
+        set_wide_tiles();  // ranks 33-128: their own kernels and tiles (psgd_wide.hip), no fused forms
+        red_even_cap = std::max<int64_t>(red_even_cap, int64_t(red_even.size()));
+        red_odd_cap = std::max<int64_t>(red_odd_cap, int64_t(red_odd.size()));
     } else {
         set_vec(base_vec);
     }
@@ -631,10 +704,25 @@ void psgd_plan::layout(int num_tensors) {
     f64_apply.carve(off, atleast1(int64_t(f64_apply.size())));
     f64_part_off.carve(off, atleast1(int64_t(f64_part_off.size())));
     o_f64_part = scratch(atleast1(f64_part) * sizeof(double));
-    o_part = scratch(size_t(part_cap) * sizeof(float));
+    o_part = scratch(wide() ? 256 : size_t(part_cap) * sizeof(float));  // wide plans: o_wide_part
     if (qfold_ok) {
         o_gram = scratch(size_t(red_even_cap) * kGramStride * sizeof(double));
         uitems.carve(off, 2 * units_q.size());
+    }
+    if (wide()) {  // behind everything else: the other plans' carve does not move
+        wide_even.carve(off, atleast1(int64_t(wide_even.size())));
+        wide_odd.carve(off, atleast1(int64_t(wide_odd.size())));
+        wide_apply.carve(off, atleast1(int64_t(wide_apply.size())));
+        o_wide_part = scratch(atleast1(wide_part) * sizeof(float));
+        wide_gp.carve(off, atleast1(int64_t(wide_gp.size())));
+        wide_gq.carve(off, atleast1(int64_t(wide_gq.size())));
+        wide_slot_p.carve(off, atleast1(int64_t(wide_slot_p.size())));
+        wide_slot_q.carve(off, atleast1(int64_t(wide_slot_q.size())));
+        const size_t rr = size_t(rbucket) * rbucket, nu = std::max(units_p.size(), units_q.size());
+        o_wide_gram = scratch(atleast1(wide_slots) * rr * sizeof(double));
+        o_wide_m = scratch(nu * rr * sizeof(double));
+        o_wide_sg = scratch(nu * size_t(rbucket) * sizeof(double));
+        o_wide_ok = scratch(nu * sizeof(int32_t));
     }
     ws_bytes = off;
 }

@@ -333,6 +333,59 @@ hipError_t launch_f64_reduce(int R, const F64Args& a, int nitems, hipStream_t s)
 hipError_t launch_f64_apply(int R, const F64Args& a, int ntiles, hipStream_t s);
 hipError_t launch_f64_orth(int R, const F64OrthArgs& a, int nunits, hipStream_t s);
 
+// ------------------------------------------------------------------ wide ranks (33-128)
+// fp32/bf16 plans whose rank bucket is 64 or 128 (psgd_wide.hip): the products and the apply
+// pass on v_mfma_f32_16x16x4_f32, their own tiles and partials, none of the fused forms. Same
+// plan layout (MatDesc, OrthUnit, P/Q offsets, factor history) as the ranks <= 32. MatDesc
+// fields as the wide tiling uses them (psgd_plan::set_wide_tiles):
+//   even product: tile (mat, strip = 64-column block, chunk = block of chunk_rows rows),
+//                 partials [nchunk][m][r] at part_even (floats from the wide partial region)
+//   odd product:  tile (mat, strip = block of odd_sw columns, chunk = 64-row block),
+//                 partials [odd_nstrip][n][r] at part_odd
+//   apply:        tile (mat, strip = block of kWideApplyCols columns, chunk = 64-row block)
+constexpr int kWideOut = 64;        // out-factor rows per workgroup (16 per wave)
+constexpr int kWideStep = 64;       // summed gradient rows / columns per loop step
+constexpr int kWideApplyCols = 256; // columns per apply tile
+
+struct WideArgs {
+    const MatDesc* mats;
+    const Tile* tiles;
+    void* const* grads;       // G_0 (in), residual (out, apply)
+    const float* x;           // orthonormal in-factor (products)
+    float* part;              // wide partial region
+    Terms res;                // local terms (products: earlier iterations; apply: all)
+    int32_t nres;
+    Terms apx;                // all-reduced terms (apply), scaled by alpha
+    float alpha;
+    int32_t shared;           // apply: apx == res and alpha == 1 (world size 1)
+    void* out;                // flat output (apply)
+    float* y;                 // out-factor state (reduce)
+    float* yh;                // its history copy
+    const RedItem* items;     // reduction items (mat, start, cnt, np)
+    int32_t even;
+};
+hipError_t launch_wide_product(int dtype, int R, bool even, const WideArgs& a, int ntiles, hipStream_t s);
+hipError_t launch_wide_reduce(const WideArgs& a, int nitems, hipStream_t s);
+hipError_t launch_wide_apply(int dtype, int R, const WideArgs& a, int ntiles, hipStream_t s);
+// Orthonormalisation of a wide plan's units in three launches (psgd_wide.hip): the panels' Gram
+// matrices over row blocks of kWideGramRows rows, one workgroup per unit for the r x r chain
+// (rank-1 units: the joint group norm; rejected panels: Householder QR), then Y = X M' over the
+// same row blocks.
+constexpr int kWideGramRows = 512;
+struct WideOrthArgs {
+    const OrthUnit* units;
+    const Tile* items;     // (mat = unit, strip = row block of the panel, chunk = partial slot)
+    const int32_t* slot0;  // per unit: its first partial slot
+    float* state;          // in-factor state buffer, orthonormalised in place
+    float* hx;             // history copy of the orthonormal in-factor
+    float* save;           // if non-null: copy of the pre-orthonormalisation values
+    double* gram;          // per slot an R x R Gram partial (blocks on and above the diagonal)
+    double* m;             // per unit M = R^-1 (R x R, row-major, upper triangular)
+    double* sg;            // per unit LAPACK's column signs (R entries)
+    int32_t* ok;           // per unit: 1 = the panel is X M D (third launch), 0 = already done
+};
+hipError_t launch_wide_orth(int R, const WideOrthArgs& a, int nunits, int nitems, hipStream_t s);
+
 // Host-side launchers (psgd_kernels*.hip). Return hipError_t.
 hipError_t launch_product(int dtype, int R, bool even, int nres, const ProductArgs& a,
                           int ntiles, hipStream_t s);

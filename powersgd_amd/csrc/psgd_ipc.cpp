@@ -158,6 +158,7 @@ int psgd_ipc_create(psgd_plan* p, int64_t flat_numel, void* handle_out) {
     if (!p || !handle_out) return fail(PSGD_ERR_VALUE, "null argument");
     if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
     if (p->f64()) return fail(PSGD_ERR_DTYPE, "the IPC all-reduce takes fp32/bf16 plans");
+    if (p->wide()) return fail(PSGD_ERR_VALUE, "psgd_ipc_create: ranks above 32 are not supported there");
     if (flat_numel < 0) return fail(PSGD_ERR_VALUE, "negative flat size");
     if (!p->ipc_peer.empty()) return fail(PSGD_ERR_STATE, "exchange session open (psgd_ipc_close first)");
     DevScope scope(p->device);

@@ -52,7 +52,7 @@ psgd_plan::~psgd_plan() {
 
 extern "C" {
 
-int psgd_version(void) { return 100; }
+int psgd_version(void) { return 101; }
 
 const char* psgd_last_error(void) { return g_err.c_str(); }
 
@@ -121,7 +121,9 @@ int psgd_plan_create(const int64_t* dims, const int32_t* ndims, int32_t num_tens
     }
     int maxr = 1;
     for (auto& g : p->groups) maxr = std::max(maxr, g.r);
-    if (maxr > 32) return fail(PSGD_ERR_VALUE, "effective rank above 32 is not supported by this build");
+    if (maxr > 32 && dtype == PSGD_F64)
+        return fail(PSGD_ERR_VALUE, "effective rank above 32 is not supported for fp64 plans");
+    if (maxr > 128) return fail(PSGD_ERR_VALUE, "effective rank above 128 is not supported by this build");
     p->rbucket = int(pow2ceil(maxr));
     {
         int64_t total = 0;
@@ -304,6 +306,10 @@ int psgd_plan_bind(psgd_plan* p, int32_t device, void* P, void* Q, void* workspa
     if (int st = upload_all(p->ws, p->units_p, p->units_q, p->munits_p, p->munits_q, p->f64_even, p->f64_odd,
                             p->f64_apply, p->f64_part_off))
         return st;
+    if (p->wide())  // (their lists are carved for wide plans only)
+        if (int st = upload_all(p->ws, p->wide_even, p->wide_odd, p->wide_apply, p->wide_gp, p->wide_gq, p->wide_slot_p,
+                                p->wide_slot_q))
+            return st;
     PSGD_HIP(hipMemset(p->ws + p->o_ss0, 0, size_t(std::max<int64_t>(p->ss0_cap, 1)) * sizeof(float)));
     p->bound = true;
     return PSGD_OK;
@@ -328,6 +334,10 @@ int psgd_plan_set_buckets(psgd_plan* p, int32_t nbuckets, const int32_t* group_e
     }
     if (nbuckets > 0 && prev != ng) return fail(PSGD_ERR_VALUE, "the last bucket must end at the last group");
     if (nbuckets > kMaxBuckets) return fail(PSGD_ERR_VALUE, "at most 8 buckets");
+    if (p->wide()) {
+        if (nbuckets > 1) return fail(PSGD_ERR_VALUE, "buckets are not supported for ranks above 32");
+        return PSGD_OK;  // one bucket is the whole plan: nothing to re-tile
+    }
     DevScope scope(p->device);
     if (p->bound) PSGD_HIP(hipDeviceSynchronize());  // the tile tables are rewritten below
     p->bucket_gend.assign(group_end, group_end + nbuckets);
@@ -355,6 +365,12 @@ int psgd_plan_fused_final(const psgd_plan* p, int64_t step, int32_t aggregate, i
     if (!p || !fused) return fail(PSGD_ERR_VALUE, "null argument");
     if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
     *fused = p->proj_final(step, aggregate != 0) ? 2 : p->fused_final(step, aggregate != 0) ? 1 : 0;
+    return PSGD_OK;
+}
+
+int psgd_plan_is_wide(const psgd_plan* p, int32_t* out) {
+    if (!p || !out) return fail(PSGD_ERR_VALUE, "null argument");
+    *out = p->wide() ? 1 : 0;
     return PSGD_OK;
 }
 

@@ -291,6 +291,20 @@ struct psgd_plan {
     DevList<Tile> f64_even{"f64_even"}, f64_odd{"f64_odd"}, f64_apply{"f64_apply"};
     DevList<int64_t> f64_part_off{"f64_part_off"};
     int64_t f64_part = 0;
+    // wide plans (rank bucket 64 / 128, psgd_wide.hip): tiles of the even product, the odd
+    // product and the apply pass (psgd_internal.h, WideArgs); the reduction items of both
+    // parities live in red_even / red_odd; partials (floats) in their own region, carved and
+    // uploaded for wide plans only
+    DevList<Tile> wide_even{"wide_even"}, wide_odd{"wide_odd"}, wide_apply{"wide_apply"};
+    int64_t wide_part = 0;
+    size_t o_wide_part = 0;
+    // their orthonormalisation (WideOrthArgs): per side (P units / Q units) the row-block items of
+    // the panels and each unit's first Gram-partial slot; the partials (wide_slots R x R fp64
+    // matrices), and per unit M = R^-1, the column signs and the chain's verdict
+    DevList<Tile> wide_gp{"wide_gp"}, wide_gq{"wide_gq"};
+    DevList<int32_t> wide_slot_p{"wide_slot_p"}, wide_slot_q{"wide_slot_q"};
+    int64_t wide_slots = 0;
+    size_t o_wide_gram = 0, o_wide_m = 0, o_wide_sg = 0, o_wide_ok = 0;
     bool bound = false;
     int device = -1;
     float* P = nullptr;
@@ -341,6 +355,7 @@ struct psgd_plan {
         return reinterpret_cast<double*>(ws + o_hist) + (int64_t(which) * iters + k) * fmax;
     }
     bool f64() const { return dtype == PSGD_F64; }
+    bool wide() const { return rbucket > 32; }  // effective rank 33-128 (fp32 / bf16 only)
     template <typename T>
     T* dev(size_t off) const { return reinterpret_cast<T*>(ws + off); }
     template <typename T>
@@ -349,6 +364,7 @@ struct psgd_plan {
 
     // psgd_geometry.cpp
     void set_f64_tiles();
+    void set_wide_tiles();
     void build_reduction();
     void set_vec(const std::vector<int>& vec);
     void build_oe();

@@ -43,6 +43,10 @@ int refresh_pointers(psgd_plan* p, void* const* grads, hipStream_t stream) {
     const size_t nt = p->shapes.size();
     for (size_t i = 0; i < nt; ++i)
         if (!grads[i]) return fail(PSGD_ERR_VALUE, "null gradient pointer");
+    if (p->wide()) {  // the wide kernels test each gradient's alignment themselves: no re-tiling
+        PSGD_HIP(p->grad_tab.select(grads, stream));
+        return PSGD_OK;
+    }
     const uintptr_t need = p->dtype == PSGD_F32 ? 16 : 8;
     bool same_vec = true;
     for (size_t i = 0; same_vec && i < p->mats.size(); ++i)
@@ -175,6 +179,77 @@ int decompress_f64(psgd_plan* p, void* const* grads, void* out, int64_t step, in
     return PSGD_OK;
 }
 
+// ---------------------------------------------------------------- wide plans ------
+// Effective ranks 33-128 (psgd_wide.hip), the fp64 pair's structure on fp32 factors:
+// orthonormalise the in-factor (Cholesky-QR in three launches; the all-reduced factor of the
+// previous iteration goes to history slot 2, the orthonormal one to slot 0), the product with
+// G_k formed on the matrix core, then the fixed-order partial reduction (both parities: the odd
+// product is split over column strips as well). psgd_compress never writes the gradients.
+int compress_wide(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s) {
+    if (int st = refresh_pointers(p, grads, s)) return st;
+    const bool even = p->even(step, it);
+    WideOrthArgs oa{};
+    oa.units = p->dev(even ? p->units_p : p->units_q);
+    oa.items = p->dev(even ? p->wide_gp : p->wide_gq);
+    oa.slot0 = p->dev(even ? p->wide_slot_p : p->wide_slot_q);
+    oa.state = even ? p->P : p->Q;
+    oa.hx = p->hist(0, it);
+    oa.save = it > 0 ? p->hist(2, it - 1) : nullptr;  // keep the all-reduced factor of it-1
+    oa.gram = p->dev<double>(p->o_wide_gram);
+    oa.m = p->dev<double>(p->o_wide_m);
+    oa.sg = p->dev<double>(p->o_wide_sg);
+    oa.ok = p->dev<int32_t>(p->o_wide_ok);
+    const int nunits = int(even ? p->units_p.size() : p->units_q.size());
+    PSGD_HIP(launch_wide_orth(p->rbucket, oa, nunits, int(even ? p->wide_gp.size() : p->wide_gq.size()), s));
+    WideArgs a{};
+    a.mats = p->dev(p->mats);
+    a.tiles = p->dev(even ? p->wide_even : p->wide_odd);
+    a.grads = p->grad_tab.table();
+    a.x = p->hist(0, it);
+    a.part = p->dev<float>(p->o_wide_part);
+    fill_terms(p, step, it, a.res);
+    a.nres = it;
+    a.y = even ? p->Q : p->P;
+    a.yh = p->hist(1, it);
+    a.items = p->dev(even ? p->red_even : p->red_odd);
+    a.even = even ? 1 : 0;
+    PSGD_HIP(launch_wide_product(p->dtype, p->rbucket, even, a, int(even ? p->wide_even.size() : p->wide_odd.size()), s));
+    PSGD_HIP(launch_wide_reduce(a, int(even ? p->red_even.size() : p->red_odd.size()), s));
+    return PSGD_OK;
+}
+
+int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s) {
+    if (int st = refresh_pointers(p, grads, s)) return st;
+    const int I = p->iters;
+    WideArgs a{};
+    a.mats = p->dev(p->mats);
+    a.tiles = p->dev(p->wide_apply);
+    a.grads = p->grad_tab.table();
+    a.out = out;
+    fill_terms(p, step, I, a.res);
+    float* last = p->even(step, I - 1) ? p->Q : p->P;  // all-reduced factor of the last iteration
+    for (int k = 0; k < kMaxTerms; ++k) a.apx.p[k] = a.apx.q[k] = nullptr;
+    for (int k = 0; k < I; ++k) {
+        const bool e = p->even(step, k);
+        float* ybar = k + 1 < I ? p->hist(2, k) : last;
+        a.apx.p[k] = e ? p->hist(0, k) : ybar;
+        a.apx.q[k] = e ? ybar : p->hist(0, k);
+    }
+    a.nres = I;
+    a.alpha = float(1.0 / double(world));  // reference alpha = 1 / num_workers (:218)
+    a.shared = world == 1 ? 1 : 0;         // the all-reduced factors are the local ones
+    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    if (int st = timing_begin(p, s, &ev, true)) return st;
+    TimedScope ts(ev);
+    PSGD_HIP(launch_wide_apply(p->dtype, p->rbucket, a, int(p->wide_apply.size()), s));
+    return PSGD_OK;
+}
+
+int refuse_wide(const psgd_plan* p, const char* what) {
+    if (!p->wide()) return PSGD_OK;
+    return fail(PSGD_ERR_VALUE, std::string(what) + ": ranks above 32 are not supported there");
+}
+
 // Diagnostic (PSGD_EVEN_STAMPS=<file>, with a library built -DPSGD_EVEN_STAMPS): after every
 // k_even launch, synchronise and append its per-workgroup stamps to <file>: one line per launch,
 // "nwg", then per workgroup its segments' gradient bytes and the kEvenStamps words
@@ -228,6 +303,7 @@ int even_stamps_end(psgd_plan* p, const ProductArgs& pa, hipStream_t s) {
 
 int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s, StepCtx c) {
     if (p->f64()) return compress_f64(p, grads, step, it, s);
+    if (p->wide()) return compress_wide(p, grads, step, it, s);
     if (int st = refresh_pointers(p, grads, s)) return st;
     const psgd_plan::Span sp = c.span ? *c.span : p->full_span();
     const bool even = p->even(step, it);
@@ -422,6 +498,7 @@ int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t 
 int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s,
                           StepCtx c) {
     if (p->f64()) return decompress_f64(p, grads, out, step, world, s);
+    if (p->wide()) return decompress_wide(p, grads, out, step, world, s);
     if (int st = refresh_pointers(p, grads, s)) return st;
     const psgd_plan::Span sp = c.span ? *c.span : p->full_span();
     const int nt = sp.tiles[1] - sp.tiles[0];
@@ -464,6 +541,7 @@ namespace {
 
 int bucket_span(const psgd_plan* p, int32_t b, psgd_plan::Span* sp) {
     if (p->f64()) return fail(PSGD_ERR_DTYPE, "buckets are not supported for fp64 plans");
+    if (int st = refuse_wide(p, "psgd_compress_bucket / psgd_decompress_bucket")) return st;
     if (p->spans.empty()) {
         if (b != 0) return fail(PSGD_ERR_VALUE, "bucket out of range");
         *sp = p->full_span();
@@ -514,7 +592,7 @@ int aggregate_comm_body(psgd_plan* p, void* const* grads, void* out, int64_t ste
     // x / W into the flat buffer, x = 0 (utils.py:43-47, powersgd.py:29-30): inside the first
     // even product's launch when the step starts even, else its own launch
     FlatArgs fa{};
-    const bool fold = has_flat && p->even(step, 0);
+    const bool fold = has_flat && p->even(step, 0) && !p->wide();  // wide products carry no flat pack
     if (fold) {
         if (int st = flat_args(f, unc, flat_out, world, s, &fa)) return st;
     } else if (has_flat) {
@@ -600,7 +678,7 @@ int psgd_aggregate_flat(psgd_plan* p, void* const* grads, void* out, int64_t ste
     if (!p->bound || !f->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
     if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
     if (reinterpret_cast<uintptr_t>(out) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
-    if (f->dtype != p->dtype || f->device != p->device || p->f64()) {  // separate launches
+    if (f->dtype != p->dtype || f->device != p->device || p->f64() || p->wide()) {  // separate launches
         if (int st = psgd_aggregate(p, grads, out, step, stream)) return st;
         return psgd_flat_pack(f, unc, flat_out, 1, stream);
     }
@@ -647,6 +725,7 @@ int psgd_product(psgd_plan* p, void* const* grads, int32_t odd, const float* x, 
                  const float* const* term_p, const float* const* term_q, void* stream) {
     if (!p || !grads || !x || !y) return fail(PSGD_ERR_VALUE, "null argument");
     if (p->f64()) return fail(PSGD_ERR_DTYPE, "the building blocks take fp32/bf16 plans");
+    if (int st = refuse_wide(p, "psgd_product")) return st;
     if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
     if (int st = check_terms(nterms, term_p, term_q)) return st;
     DevScope scope(p->device);
@@ -694,6 +773,7 @@ int psgd_orthogonalize(psgd_plan* p, int32_t which, float* buf, int32_t mode, vo
     if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
     if (mode != 0 && mode != 1) return fail(PSGD_ERR_VALUE, "mode must be 0 (reference) or 1 (paper-code)");
     if (p->f64()) return fail(PSGD_ERR_DTYPE, "the building blocks take fp32/bf16 plans");
+    if (int st = refuse_wide(p, "psgd_orthogonalize")) return st;
     DevScope scope(p->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     OrthArgs oa{};
@@ -717,6 +797,7 @@ int psgd_reconstruct(psgd_plan* p, void* const* grads, void* const* resid_out, v
     if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
     if (nterms < 1) return fail(PSGD_ERR_VALUE, "at least one term");
     if (p->f64()) return fail(PSGD_ERR_DTYPE, "the building blocks take fp32/bf16 plans");
+    if (int st = refuse_wide(p, "psgd_reconstruct")) return st;
     if (int st = check_terms(nterms, term_p, term_q)) return st;
     if (int st = check_terms(nterms, avg_p, avg_q)) return st;
     DevScope scope(p->device);

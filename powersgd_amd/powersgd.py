@@ -16,6 +16,10 @@ Differences, all deliberate:
   gradient matrix is read/written in bf16, factors and arithmetic stay fp32.
 * float64 gradients (the reference's own test dtype) run fp64 kernels with fp64 factors; as in
   the reference, torch's default dtype must then be float64 (P/Q follow it, :241-251).
+* The effective rank ``min(rank, n, m)`` of a matrix is at most 128 for float32 / bfloat16
+  gradients and at most 32 for float64 ones (the reference has no limit); the constructor raises
+  ``ValueError`` beyond. Above 32, a step keeps one collective per iteration (no buckets) and the
+  IPC exchange (``PSGD_COMM=ipc``) is not available.
 * Returned compressed outputs are views of one flat buffer (allocated fresh per call)
   instead of separate ``empty_like`` tensors; uncompressed outputs are views in the
   reference too.
@@ -330,6 +334,9 @@ class BasicPowerSGD(Aggregator):
         uncompressed values), all-gather the IPC handles and open the peers' buffers."""
         if self._ipc_open:
             return
+        if self._plan.is_wide():
+            raise RuntimeError("PSGD_COMM=ipc supports effective ranks up to 32; this plan's rank exceeds that "
+                               "(ranks 33-128 run over PSGD_COMM=rccl or PSGD_COMM=torch)")
         dist = torch.distributed
         world = dist.get_world_size()
         handle = self._plan.ipc_create(flat_numel)
@@ -475,11 +482,12 @@ class BasicPowerSGD(Aggregator):
         issued per bucket slice, asynchronously, right after that bucket's kernels: bucket b's
         collective overlaps bucket b+1's product (RCCL runs on its own stream), and the next
         iteration of bucket b waits only for bucket b's collective. SUM over slices == SUM over
-        the whole buffer, element by element. fp64 plans and PSGD_BUCKETS=1 keep one collective."""
+        the whole buffer, element by element. fp64 plans, plans of effective rank above 32 and
+        PSGD_BUCKETS=1 keep one collective."""
         if want is None:
             want = int(os.environ.get("PSGD_BUCKETS", "4"))
         groups = self._plan.groups()
-        if self.dtype == torch.float64 or want <= 1 or len(groups) < 2:
+        if self.dtype == torch.float64 or self._plan.is_wide() or want <= 1 or len(groups) < 2:
             self._buckets = [(0, self._ps_buffer.numel(), 0, self._qs_buffer.numel())]
             return
         cost = [c * n * m for n, m, _r, c in groups]

@@ -43,6 +43,9 @@ class _Codec:
         self.shapes = [t.shape for t in tensors]
         # the codec's matrix view is [shape[0], numel/shape[0]] (as the paper's view(n, -1))
         self.plan = _lib.Plan([tuple(s) for s in self.shapes], rank, 2, _dtype_code(t0.dtype))
+        if self.plan.is_wide():  # the building blocks would refuse at the first product
+            raise ValueError(f"paper-code reducers (rank={rank}): ranks above 32 are not supported there; "
+                             "PowerSGD / BasicPowerSGD take effective ranks up to 128")
         pn, qn = self.plan.factor_numel()
         self.P = torch.zeros(pn, dtype=torch.float32, device=self.device)
         self.Q = torch.zeros(qn, dtype=torch.float32, device=self.device)

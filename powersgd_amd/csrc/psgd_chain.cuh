@@ -1,4 +1,4 @@
-// Panel helpers shared by the orthonormalisation kernels (psgd_small.hip) and the projection
+// Panel helpers shared by the orthonormalisation kernels (psgd_orth.hip) and the projection
 // form's in-pass Cholesky-QR (psgd_final.cuh): panel row loads/stores, fp64 wave sums, the
 // Cholesky-QR chain with LAPACK column signs, and the exact Householder QR (geqr2 + org2r)
 // that rejected panels take (reference powersgd/orthogonalization.py:8, torch.linalg.qr).

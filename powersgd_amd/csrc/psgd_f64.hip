@@ -2,7 +2,7 @@
 // torch.set_default_dtype(torch.float64)). There the P/Q factors follow the default dtype
 // (powersgd.py:241-251), so gradients, factors and every product are fp64. This file is the
 // codec for that case, kernel for kernel the fp32 path's structure (psgd_stream.cuh,
-// psgd_small.hip) without its fusions:
+// psgd_reduce.hip, psgd_orth.hip) without its fusions:
 //
 //   k_f64_even   Q_part = G_k^T X per (64-column strip, 256-row chunk) tile, one partial per
 //                wave (no atomics)                           reference powersgd.py:185-193

@@ -386,9 +386,9 @@ struct WideOrthArgs {
 };
 hipError_t launch_wide_orth(int R, const WideOrthArgs& a, int nunits, int nitems, hipStream_t s);
 
-// Host-side launchers (psgd_kernels*.hip). Return hipError_t.
-hipError_t launch_product(int dtype, int R, bool even, int nres, const ProductArgs& a,
-                          int ntiles, hipStream_t s);
+// Host-side launchers, grouped by the unit that defines them. Return hipError_t.
+// psgd_step.cpp: by dtype to the launchers of psgd_{product,apply,final}_{f32,bf16}.hip and
+// psgd_f64.hip (psgd_plan.h)
 hipError_t launch_odd_mfma(int dtype, int R, int nres, const ProductArgs& a, int ntiles,
                            hipStream_t s);
 hipError_t launch_apply(int dtype, int R, int nterms, bool shared, const ApplyArgs& a,
@@ -397,11 +397,14 @@ hipError_t launch_apply(int dtype, int R, int nterms, bool shared, const ApplyAr
 hipError_t launch_final_odd(int dtype, int R, int nres, int smax, const FinalArgs& a, int ntiles,
                             hipStream_t s, int* waves = nullptr);
 hipError_t launch_lowrank_out(int dtype, int R, int nterms, const ApplyArgs& a, int ntiles, hipStream_t s);
+// psgd_reduce.hip
 hipError_t launch_reduce(const ReduceArgs& a, int nitems, hipStream_t s);
+// psgd_orth.hip
 hipError_t launch_orth(const OrthArgs& a, int nunits, int R, int64_t max_rows, bool chol, hipStream_t s);
 hipError_t launch_orth_chain(const ChainArgs& a, int nunits, int64_t max_rows, int R, hipStream_t s);
 // paper-code Gram-Schmidt (gradient_reducers.py:945-956) on one panel per unit, per matrix
 hipError_t launch_orth_mgs(const OrthArgs& a, int nunits, int R, hipStream_t s);
+// psgd_pack.hip (fp64: psgd_f64.hip)
 hipError_t launch_flat_pack(int dtype, const FlatArgs& a, hipStream_t s);
 hipError_t launch_flat_pack_f64(const FlatArgs& a, hipStream_t s);
 
@@ -418,7 +421,7 @@ struct RunsArgs {
     void* const* tensors;
     int32_t nitems;
 };
-hipError_t launch_runs(int dtype, bool add, const RunsArgs& a, hipStream_t s);
+hipError_t launch_runs(int dtype, bool add, const RunsArgs& a, hipStream_t s);  // psgd_pack.hip
 
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),
@@ -468,6 +471,6 @@ struct XchgArgs {
     double* gram;
     int32_t gram_r;
 };
-hipError_t launch_xchg(const XchgArgs& a, hipStream_t s);
+hipError_t launch_xchg(const XchgArgs& a, hipStream_t s);  // psgd_xchg.hip
 
 }  // namespace psgd

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(kBlock) void k_wide_apply(WideArgs a) {
 // ---------------------------------------------------------------- orthonormalise --
 // Q of the Householder QR of each [k, r] panel X with LAPACK's column signs (reference
 // orthogonalization.py:8, torch.linalg.qr), computed as Q = X R^-1 D like k_orth_chol /
-// orth_chol_wide (psgd_small.hip), whose single workgroup per panel cannot hold a 64 / 128
+// orth_chol_wide (psgd_orth_chol.cuh), whose single workgroup per panel cannot hold a 64 / 128
 // column chain. Three launches:
 //   k_wide_gram        G = X^T X in fp64 on v_mfma_f64_16x16x4_f64, one workgroup per block of
 //                      kWideGramRows panel rows (blocks on and above the diagonal, spread over the

@@ -139,3 +139,41 @@ def test_panel_length_instances(rank, k):
                                ("q", psgd._powersgd._qs_buffer, ora.codec.q_flat)):
             err = float((gpu.cpu() - ref).abs().max()) / max(1.0, float(ref.abs().max()))
             check(err, 1e-5, "orth_panel_len_" + name, rank, k, t)
+
+
+# the last panel length of every Householder kernel instance and the first of the next one
+_POW2_EDGES = [64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025, 2048, 2049, 4096, 4097, 8192, 8193]
+HOUSEHOLDER_CASES = ([(2, k) for k in _POW2_EDGES + [16384, 16385]] + [(4, k) for k in _POW2_EDGES] +
+                     [(8, k) for k in (64, 65, 128, 129, 1024, 1025, 2048, 2049)])
+
+
+@pytest.mark.parametrize("rank,k", HOUSEHOLDER_CASES)
+def test_householder_instances(rank, k):
+    """With PSGD_ORTH_CHOL=0 the launch's longest panel alone selects the Householder kernel
+    and its instance (k_orth_wy<R, RPT, NW> by rows per thread and waves per panel, then
+    k_orth_reg<R, RPT>, then the LDS / in-place k_orth<R>): a panel at each side of every
+    boundary, beside short panels of the same launch, against the oracle's LAPACK state.
+    Step 0 orthonormalises the P panels (k rows), step 1 the Q panels."""
+    old = os.environ.get("PSGD_ORTH_CHOL")
+    os.environ["PSGD_ORTH_CHOL"] = "0"
+    try:
+        shapes = [(k, 16), (16, k), (64, 8), (5, 40)]
+        psgd = PowerSGD([torch.zeros(s, device=DEV) for s in shapes], Config(rank, 0.1, 1, 0))
+        ora = O.policy_init([torch.zeros(s) for s in shapes], rank, 0.1, 1, 0)
+        ora.codec.p_flat.copy_(psgd._powersgd._ps_buffer.cpu())
+        ora.codec.q_flat.copy_(psgd._powersgd._qs_buffer.cpu())
+        for t in range(2):
+            g = [torch.from_numpy(f) for f in hash_tensors(shapes, seed=41 + t)]
+            psgd.aggregate([x.to(DEV) for x in g])
+            O.policy_step(ora, [x.clone() for x in g])
+            torch.cuda.synchronize()
+            # 1e-5 of the buffer's largest entry, as in test_panel_length_instances
+            for name, gpu, ref in (("p", psgd._powersgd._ps_buffer, ora.codec.p_flat),
+                                   ("q", psgd._powersgd._qs_buffer, ora.codec.q_flat)):
+                err = float((gpu.cpu() - ref).abs().max()) / max(1.0, float(ref.abs().max()))
+                check(err, 1e-5, "orth_householder_" + name, rank, k, t)
+    finally:
+        if old is None:
+            os.environ.pop("PSGD_ORTH_CHOL", None)
+        else:
+            os.environ["PSGD_ORTH_CHOL"] = old

@@ -1,5 +1,5 @@
 """GPU parity of the folded Q orthonormalisation of the projection form (k_reduce's per-item
-Gram partials + k_orth_chain, powersgd_amd/csrc/psgd_small.hip).
+Gram partials + k_orth_chain, powersgd_amd/csrc/psgd_reduce.hip, psgd_orth_chol.cuh).
 
 Two-iteration rank-2/4 plans at world size 1 orthonormalise the even iteration's Q from Gram
 partials the reduction left, one workgroup per (panel, 1024-row slice). Pinned against:

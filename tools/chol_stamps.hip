@@ -1,8 +1,8 @@
-// Diagnostic build: k_orth_chol<4> with s_memtime phase stamps (psgd_small.hip, PSGD_STAMPS):
+// Diagnostic build: k_orth_chol<4> with s_memtime phase stamps (psgd_orth.hip, PSGD_STAMPS):
 // workgroup 0 takes a k-row panel, the other units are ResNet-50-like Q panels.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DPSGD_STAMPS -I include -I powersgd_amd/csrc \
 //         tools/chol_stamps.hip -o tools/chol_stamps
-#include "../powersgd_amd/csrc/psgd_small.hip"
+#include "../powersgd_amd/csrc/psgd_orth.hip"
 
 #include <cstdio>
 #include <vector>

@@ -1,9 +1,9 @@
 // Diagnostic build: the orthonormalisation kernels with s_memtime phase stamps
-// (psgd_small.hip, PSGD_STAMPS; rank-4 panels through launch_orth, i.e. k_orth_wy).
+// (psgd_orth.hip, PSGD_STAMPS; rank-4 panels through launch_orth, i.e. k_orth_wy).
 // Prints shader-clock cycles per phase and the hipEvent duration of one launch.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DPSGD_STAMPS -I include -I powersgd_amd/csrc \
 //         tools/orth_stamps.hip -o tools/orth_stamps
-#include "../powersgd_amd/csrc/psgd_small.hip"
+#include "../powersgd_amd/csrc/psgd_orth.hip"
 
 #include <cstdio>
 #include <vector>

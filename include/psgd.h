@@ -329,6 +329,30 @@ int psgd_runs_bind(psgd_runs* runs, int32_t device, void* workspace);
 int psgd_runs_add(psgd_runs* runs, const void* bucket, void* const* tensors, void* stream);
 int psgd_runs_gather(psgd_runs* runs, void* bucket, void* const* tensors, void* stream);
 
+/* Run tables whose two sides differ: a bucket-side dtype and a tensor-side dtype, and optionally
+ * a bucket side made of separate tensors. Accepted pairs: the three equal pairs (then exactly
+ * psgd_runs_create) and (bucket PSGD_BF16, tensors PSGD_F32): an fp32 error-feedback residual fed
+ * by bf16 gradients. Any other pair: PSGD_ERR_DTYPE. For the mixed pair
+ *   add:    tensors[..] = tensors[..] + float(bucket[..])   exact upcast, ONE fp32 add, nothing is
+ *                                                            rounded to bf16
+ *   gather: bucket[..]  = bf16(tensors[..])                 round to nearest even
+ * `source` null: the bucket side is one buffer; the table is driven by psgd_runs_add /
+ * psgd_runs_gather as above (a DDP bucket). `source` given (nruns indices below nsources): run k's
+ * bucket side is sources[source[k]] + bucket_off[k], `sources` a host array of nsources device
+ * pointers passed at call time and uploaded when it changes, like `tensors` (the optimizer_step
+ * flow, whose "bucket" is the caller's separate gradient tensors); such a table is driven by
+ * psgd_runs_add_list / psgd_runs_gather_list. zero_source != 0: the add also stores +0.0 to every
+ * source element it read (the gradients are consumed in the pass that reads them). One launch per
+ * call, 2-byte / 4-byte alignment of the two sides independently. Calling the form the table was
+ * not created for is PSGD_ERR_STATE. The workspace (psgd_runs_workspace_bytes) holds both pointer
+ * tables. */
+int psgd_runs_create_mixed(const int64_t* bucket_off, const int32_t* tensor, const int64_t* tensor_off,
+                           const int64_t* len, const int32_t* source, int32_t nruns, int32_t ntensors,
+                           int32_t nsources, int32_t bucket_dtype, int32_t tensor_dtype, psgd_runs** out);
+int psgd_runs_add_list(psgd_runs* runs, void* const* sources, void* const* tensors, int32_t zero_source,
+                       void* stream);
+int psgd_runs_gather_list(psgd_runs* runs, void* const* sources, void* const* tensors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

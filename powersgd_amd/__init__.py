@@ -10,9 +10,10 @@ C ABI in include/psgd.h); the factor all-reduce uses torch.distributed (RCCL on 
 import torch
 
 from powersgd_amd.powersgd import Aggregator, AllReduce, Config, PowerSGD  # noqa: F401
+from powersgd_amd.residual import Fp32ResidualPowerSGD  # noqa: F401
 from powersgd_amd.utils import params_in_optimizer
 
-__all__ = ["Aggregator", "AllReduce", "Config", "PowerSGD", "optimizer_step"]
+__all__ = ["Aggregator", "AllReduce", "Config", "Fp32ResidualPowerSGD", "PowerSGD", "optimizer_step"]
 
 
 def optimizer_step(optimizer: torch.optim.Optimizer, aggregator: Aggregator):

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PSGD_LIB_PATH: an alternative in-tree build (tuning variants); default the standard one
@@ -73,6 +73,10 @@ _SIGNATURES = {
     "psgd_runs_bind": ([_vp, _i32, _vp], _i32),
     "psgd_runs_add": ([_vp, _vp, _vp, _vp], _i32),
     "psgd_runs_gather": ([_vp, _vp, _vp, _vp], _i32),
+    "psgd_runs_create_mixed": ([_P_i64, _P_i32, _P_i64, _P_i64, _P_i32, _i32, _i32, _i32, _i32, _i32,
+                                ctypes.POINTER(_vp)], _i32),
+    "psgd_runs_add_list": ([_vp, _vp, _vp, _i32, _vp], _i32),
+    "psgd_runs_gather_list": ([_vp, _vp, _vp, _vp], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -341,15 +345,27 @@ class FlatPlan:
 
 class Runs:
     """Owns a psgd_runs: a DDP bucket's flat buffer <-> per-parameter tensors (run table, 64-bit
-    offsets). ``add``: tensors += bucket (error-feedback add); ``gather``: bucket = tensors."""
+    offsets). ``add``: tensors += bucket (error-feedback add); ``gather``: bucket = tensors.
+
+    ``bucket_dtype_code`` (default: ``dtype_code``) is the bucket side's dtype
+    (psgd_runs_create_mixed: the equal pairs, or a bf16 bucket side over fp32 tensors). With
+    ``source`` (one index below ``nsources`` per run) the bucket side is a table of separate
+    tensors, driven by ``add_list`` / ``gather_list`` instead of ``add`` / ``gather``."""
 
     def __init__(self, bucket_off: Sequence[int], tensor: Sequence[int], tensor_off: Sequence[int],
-                 length: Sequence[int], ntensors: int, dtype_code: int):
+                 length: Sequence[int], ntensors: int, dtype_code: int, bucket_dtype_code: Optional[int] = None,
+                 source: Optional[Sequence[int]] = None, nsources: int = 0):
         n = len(length)
         h = _vp()
-        check(lib().psgd_runs_create((_i64 * max(1, n))(*bucket_off), (_i32 * max(1, n))(*tensor),
-                                     (_i64 * max(1, n))(*tensor_off), (_i64 * max(1, n))(*length), n, ntensors,
-                                     dtype_code, ctypes.byref(h)))
+        arrays = ((_i64 * max(1, n))(*bucket_off), (_i32 * max(1, n))(*tensor), (_i64 * max(1, n))(*tensor_off),
+                  (_i64 * max(1, n))(*length))
+        if bucket_dtype_code is None and source is None:
+            check(lib().psgd_runs_create(*arrays, n, ntensors, dtype_code, ctypes.byref(h)))
+        else:
+            src = None if source is None else (_i32 * max(1, n))(*source)
+            check(lib().psgd_runs_create_mixed(*arrays, src, n, ntensors, nsources,
+                                               dtype_code if bucket_dtype_code is None else bucket_dtype_code,
+                                               dtype_code, ctypes.byref(h)))
         self._h = h
 
     def __del__(self):
@@ -371,6 +387,12 @@ class Runs:
 
     def gather(self, bucket_ptr: int, tensors, stream: int) -> None:
         check(lib().psgd_runs_gather(self._h, bucket_ptr, tensors, stream))
+
+    def add_list(self, sources, tensors, zero_source: bool, stream: int) -> None:
+        check(lib().psgd_runs_add_list(self._h, sources, tensors, 1 if zero_source else 0, stream))
+
+    def gather_list(self, sources, tensors, stream: int) -> None:
+        check(lib().psgd_runs_gather_list(self._h, sources, tensors, stream))
 
 
 def comm_unique_id() -> bytes:

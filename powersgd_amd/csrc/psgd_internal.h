@@ -423,6 +423,20 @@ struct RunsArgs {
 };
 hipError_t launch_runs(int dtype, bool add, const RunsArgs& a, hipStream_t s);  // psgd_pack.hip
 
+// The run tables of psgd_runs_create_mixed that k_runs does not serve: a bf16 bucket side over
+// fp32 tensors (the fp32 error-feedback residual of bf16 gradients), and the source-table form,
+// where item i's bucket side is sources[src[i]] instead of one base pointer (`src` null: `bucket`).
+enum RunsMode { kRunsGather = 0, kRunsAdd = 1, kRunsAddZero = 2 };  // AddZero: ADD, then bucket = +0.0
+struct RunsMixArgs {
+    const RunItem* items;
+    const int32_t* src;      // per item: its source index (source-table form), else null
+    void* bucket;            // single-bucket form
+    void* const* sources;    // source-table form
+    void* const* tensors;
+    int32_t nitems;
+};
+hipError_t launch_runs_mix(int bucket_dtype, int tensor_dtype, int mode, const RunsMixArgs& a, hipStream_t s);
+
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),
 // then two parities x iterations slots of xchg_slot floats each; the producer kernels (k_reduce,

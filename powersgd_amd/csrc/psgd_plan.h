@@ -402,7 +402,8 @@ struct psgd_flat {
 // DDP bucket <-> parameter tensors (psgd_runs_*, include/psgd.h): the work items of one run
 // table and the device pointer tables of the tensors it addresses
 struct psgd_runs {
-    int dtype = 0;
+    int dtype = 0;         // the tensors' dtype
+    int bucket_dtype = 0;  // the bucket side's (psgd_runs_create_mixed; else == dtype)
     int32_t ntensors = 0;
     DevList<RunItem> items{"run items"};
     int64_t bucket_numel = 0;  // one past the last bucket element any run touches
@@ -411,6 +412,13 @@ struct psgd_runs {
     int device = -1;
     char* ws = nullptr;
     TableCache tab;
+    // source-table form: the bucket side is nsources separate tensors; per item its source index,
+    // and the sources' device pointer tables (change-detected like the tensors')
+    bool listed = false;
+    int32_t nsources = 0;
+    DevList<int32_t> item_src{"run item sources"};
+    size_t o_src = 0;
+    TableCache src_tab;
 };
 
 namespace psgd {

@@ -47,21 +47,30 @@ class _BucketRuns:
     """The run table of one DDP bucket layout (one run per parameter: bucket offset, parameter
     index, length), bound to device memory (psgd_runs_*)."""
 
-    def __init__(self, key, buf: torch.Tensor, grads, idx, ntensors: int, code: int, dev_index: int):
+    def __init__(self, key, buf: torch.Tensor, grads, idx, ntensors: int, code: int, dev_index: int,
+                 bucket_code: Optional[int] = None):
         self.key = key
         esz = buf.element_size()
         self.offs = [(g.data_ptr() - buf.data_ptr()) // esz for g in grads]
         self.idx = list(idx)
         self.lens = [g.numel() for g in grads]
-        self.runs = _lib.Runs(self.offs, self.idx, [0] * len(idx), self.lens, ntensors, code)
+        # bucket_code: the bucket's dtype where it differs from the residual's (bf16 over fp32)
+        self.runs = _lib.Runs(self.offs, self.idx, [0] * len(idx), self.lens, ntensors, code, bucket_code)
         self.ws = torch.empty(self.runs.workspace_bytes(), dtype=torch.uint8, device=buf.device)
         self.runs.bind(dev_index, self.ws.data_ptr())
 
 
 class PowerSGDState:
-    """Hook state: one codec + residual buffer over ``params`` (the optimizer's order)."""
+    """Hook state: one codec + residual buffer over ``params`` (the optimizer's order).
 
-    def __init__(self, config: Config, params, process_group=None):
+    ``residual_dtype=torch.float32`` with bfloat16 parameters keeps the error-feedback residual in
+    fp32: each bf16 bucket is upcast exactly and added in fp32 (a bf16 residual drops every fresh
+    component below 2^-8 of the element it lands on), the codec and the uncompressed average run
+    in fp32 on the residual, and DDP gets the bf16 rounding of the fp32 average back. ``None``
+    (default): the residual has the parameters' dtype. 4 bytes of state per parameter instead
+    of 2."""
+
+    def __init__(self, config: Config, params, process_group=None, residual_dtype=None):
         if process_group is not None and process_group is not dist.group.WORLD:
             raise ValueError("powersgd_hook all-reduces on the default process group (reference :207)")
         self.config = config
@@ -77,11 +86,19 @@ class PowerSGDState:
         if mixed:
             raise RuntimeError(f"powersgd_hook needs one gradient dtype: parameter {mixed[0]} is "
                                f"{self.params[mixed[0]].dtype}, parameter 0 is {p0.dtype}")
+        if residual_dtype is not None and not (residual_dtype == torch.float32
+                                               and p0.dtype in (torch.float32, torch.bfloat16)):
+            raise ValueError(f"residual_dtype must be None, or torch.float32 with float32 / bfloat16 parameters; "
+                             f"got {residual_dtype} with {p0.dtype} parameters")
         self._dev_index = _require_device(p0.device)
-        self._code = _DTYPES[p0.dtype] if p0.dtype in _DTYPES else None
-        if self._code is None:
+        if p0.dtype not in _DTYPES:
             raise RuntimeError(f"powersgd_hook supports float32, bfloat16 and float64 gradients, got {p0.dtype}")
-        self.residual = torch.zeros(numel, dtype=p0.dtype, device=p0.device)
+        res_dtype = p0.dtype if residual_dtype is None else residual_dtype
+        # the residual's dtype code (run tables' tensor side, the codec, the averages) and, where the
+        # DDP buckets' dtype differs from it (bf16 buckets over an fp32 residual), the buckets'
+        self._code = _DTYPES[res_dtype]
+        self._bucket_code = _DTYPES[p0.dtype] if p0.dtype != res_dtype else None
+        self.residual = torch.zeros(numel, dtype=res_dtype, device=p0.device)
         self.views: List[torch.Tensor] = []
         off = 0
         for p in self.params:
@@ -112,11 +129,12 @@ class PowerSGDState:
                     raise RuntimeError("parameter reached powersgd_hook twice in one iteration")
                 idx.append(i)
             buf = bucket.buffer()
-            if buf.dtype != self.residual.dtype:
-                # DDP buckets carry the gradients' dtype; anything else (e.g. a bf16 bucket under
-                # an fp32 state) would be read and written at the wrong element size
+            if buf.dtype != self.params[0].dtype:
+                # DDP buckets carry the gradients' dtype (the parameters'; the residual's may be
+                # fp32 over bf16 gradients); anything else (e.g. a bf16 bucket under an fp32
+                # state) would be read and written at the wrong element size
                 raise RuntimeError(f"powersgd_hook: DDP bucket dtype {buf.dtype} differs from the state's "
-                                   f"gradient dtype {self.residual.dtype}")
+                                   f"gradient dtype {self.params[0].dtype}")
             runs = self._bucket_runs(bucket.index(), buf, grads, idx)
             self._ef_add(buf, runs)
             for i in idx:
@@ -162,7 +180,7 @@ class PowerSGDState:
         return r
 
     def _new_runs(self, key, buf, grads, idx) -> _BucketRuns:
-        return _BucketRuns(key, buf, grads, idx, len(self.params), self._code, self._dev_index)
+        return _BucketRuns(key, buf, grads, idx, len(self.params), self._code, self._dev_index, self._bucket_code)
 
     def _ef_add(self, buf: torch.Tensor, runs: _BucketRuns) -> None:
         """Error feedback: residual += the bucket's fresh gradients, the whole bucket in one launch

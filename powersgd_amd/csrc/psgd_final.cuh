@@ -77,6 +77,32 @@ __device__ __forceinline__ void fin_st(rsrc_t rs, uint32_t e, bool ok, int32_t c
     }
 }
 
+// The rank-1 prologue's sums of squares of one row block: the ranges (FinRng, loaded beside the
+// tile) and each lane's first term of the group's and the matrix's sum, whose loads went out
+// before the MatDesc load returned.
+struct FinSs {
+    int32_t gb, ge, mb, me;
+    float g0, m0;
+};
+template <int R, bool PJ>
+__device__ __forceinline__ FinSs fin_ss_begin(const FinalArgs& a, int block) {
+    FinSs f{0, 0, 0, 0, 0.f, 0.f};
+    if constexpr (R == 1) {
+        if (a.ss_in != nullptr) {
+            const FinRng fr = a.rng[block];
+            f.gb = a.rsel ? fr.g[1][0] : fr.g[0][0];
+            f.ge = a.rsel ? fr.g[1][1] : fr.g[0][1];
+            f.g0 = ss_first(a.ss_in, f.gb, f.ge);
+            if constexpr (PJ) {
+                f.mb = fr.mb;
+                f.me = fr.me;
+                f.m0 = ss_first(a.ss_in, f.mb, f.me);
+            }
+        }
+    }
+    return f;
+}
+
 // P_0 rows of a row block staged in LDS by the projection form: kFinRowsMax (psgd_internal.h)
 constexpr int kProjRows = kFinRowsMax;
 
@@ -97,7 +123,7 @@ constexpr int kProjRows = kFinRowsMax;
 // iteration k + 1 with its in-factor P_k before the joint norm, which the reduction divides
 // out), and sum_rows P^2 for that norm. The gradient is read once for both iterations.
 template <typename T, int R, int K, int SMAX, bool VEC, int NT, int RB, bool PJ = false, bool OE = false>
-__device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc& d, const Tile& t,
+__device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc& d, const Tile& t, const FinSs& fs,
                                                float* red, float* rqs = nullptr, float* oered = nullptr) {
     static_assert(!OE || (R == 1 && !PJ), "the odd-even pass is rank 1, K-term form");
     constexpr int KC = K > 0 ? K : 1;
@@ -158,13 +184,34 @@ __device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc
     // dependent round trips) then overlaps the gradient's HBM latency instead of preceding it.
     Batch ga, gb;
     load(ga, 0);
+    // Rank-1 projection form: the factor panel and this thread's first staged P_0 value go out
+    // next, beside the sums of squares whose first terms are already in flight (FinSs): one
+    // round trip for all of them, and only the division by the norm waits for the sums. The
+    // other forms load their panels after the norm as before: issued here they cost K-term and
+    // odd-even instances a wave per SIMD (profiles/seam_chains/resource_usage.md).
+    constexpr bool kEarly = PJ && R == 1;
+    const int nst = int(row_end - row0) * R;  // PJ: staged P_0 values (the plan keeps row blocks <= kProjRows rows)
+    float xe[kEarly ? SMAX : 1][4];
+    float p0v = 0.f;
+    if constexpr (kEarly) {
+#pragma unroll
+        for (int s = 0; s < SMAX; ++s)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) xe[s][v] = X[(ccol[s] + v < m ? ccol[s] + v : 0) * r];  // ld_factor<1>, fcol below
+        // element tid of the staging loop below (clamped, unconditional)
+        p0v = a.proj_p0[d.poff + (row0 + (tid < nst ? tid : 0)) * r];
+    }
     // rank-1 joint norm of the raw in-factor (world size 1, fused): x / max(||x||, eps)
-    // (rank-1 plans only: fused_norm, psgd_plan.cpp; compile-time false above rank 1)
+    // (rank-1 plans only: fused_norm, psgd_plan.cpp; compile-time false above rank 1). Both
+    // sums' loads (group and, PJ, matrix) are issued before either wave tree.
     const bool norm = R == 1 && a.ss_in != nullptr;
-    const float dn = norm ? group_norm_ss(a.ss_in, a.grng_in, d.group) : 1.f;
+    float gacc = fs.g0, macc = fs.m0;
+    if (norm) gacc = ss_tail(a.ss_in, fs.gb, fs.ge, gacc);
+    if constexpr (PJ && R == 1) macc = ss_tail(a.ss_in, fs.mb, fs.me, macc);
+    const float dn = norm ? norm_floor(wave_allsum(gacc)) : 1.f;
     float cfac = 0.f, kfac = 0.f;  // rank-1 projection: c and N - c of this matrix
     if constexpr (PJ && R == 1) {
-        cfac = range_ss(a.ss_in, a.mrng_in, t.mat) / dn;
+        cfac = wave_allsum(macc) / dn;
         kfac = dn - cfac;
     }
     if (norm && t.chunk == 0) {  // row block 0 publishes this matrix's normalised in-factor
@@ -186,8 +233,12 @@ __device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc
             else
                 rqs[tid] = (c < r && l < r) ? a.proj_r[d.qoff + c * r + l] : 0.f;
         }
-        const int nst = int(row_end - row0) * R;  // the plan keeps row blocks <= kProjRows rows
-        for (int e = tid; e < nst; e += NT) {
+        int e0 = tid;
+        if constexpr (kEarly) {
+            if (tid < nst) rqs[R * R + tid] = p0v;
+            e0 += NT;
+        }
+        for (int e = e0; e < nst; e += NT) {
             const int i = e / R, l = e - (e / R) * R;
             rqs[R * R + e] = l < r ? a.proj_p0[d.poff + (row0 + i) * r + l] : 0.f;
         }
@@ -204,7 +255,12 @@ __device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc
 #pragma unroll
         for (int s = 0; s < SMAX; ++s)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) ld_factor<R>(X + fcol(s, v) * r, r, xq[s][v]);
+            for (int v = 0; v < 4; ++v) {
+                if constexpr (kEarly)
+                    xq[s][v][0] = xe[s][v];
+                else
+                    ld_factor<R>(X + fcol(s, v) * r, r, xq[s][v]);
+            }
         if constexpr (K > 0) {
 #pragma unroll
             for (int k = 0; k < K; ++k)
@@ -484,11 +540,12 @@ __device__ __forceinline__ void final_odd_block(const FinalArgs& a) {
         return;
     }
     const Tile t = a.tiles[blockIdx.x - nf];
+    const FinSs fs = fin_ss_begin<R, PJ>(a, blockIdx.x - nf);  // beside the tile: no MatDesc hop
     const MatDesc d = a.mats[t.mat];
     if (d.vec)
-        final_odd_tile<T, R, K, SMAX, true, NT, RB, PJ>(a, d, t, red, rqs);
+        final_odd_tile<T, R, K, SMAX, true, NT, RB, PJ>(a, d, t, fs, red, rqs);
     else
-        final_odd_tile<T, R, K, SMAX, false, NT, RB, PJ>(a, d, t, red, rqs);
+        final_odd_tile<T, R, K, SMAX, false, NT, RB, PJ>(a, d, t, fs, red, rqs);
 }
 
 template <typename T, int R, int K, int SMAX>
@@ -504,11 +561,12 @@ __global__ __launch_bounds__(FinNT<1>::value) void k_final_oe(FinalArgs a) {
     __shared__ float red[2 * (NT / 64) * RB];
     __shared__ float oered[NT * SMAX * 4 + NT];
     const Tile t = a.tiles[blockIdx.x];
+    const FinSs fs = fin_ss_begin<1, false>(a, blockIdx.x);
     const MatDesc d = a.mats[t.mat];
     if (d.vec)
-        final_odd_tile<T, 1, K, SMAX, true, NT, RB, false, true>(a, d, t, red, nullptr, oered);
+        final_odd_tile<T, 1, K, SMAX, true, NT, RB, false, true>(a, d, t, fs, red, nullptr, oered);
     else
-        final_odd_tile<T, 1, K, SMAX, false, NT, RB, false, true>(a, d, t, red, nullptr, oered);
+        final_odd_tile<T, 1, K, SMAX, false, NT, RB, false, true>(a, d, t, fs, red, nullptr, oered);
 }
 
 #ifndef PSGD_PROJ1_WPE

@@ -552,7 +552,35 @@ void psgd_plan::set_vec(const std::vector<int>& vec) {
     }
     build_oe();
     build_reduction();
+    fill_seam_descriptors();
     if (!bucket_gend.empty()) build_spans();
+}
+
+// What the rank-1 prologue of the fused final passes used to reach through MatDesc and the
+// range tables, copied beside each row block: its group's and its matrix's item ranges.
+void psgd_plan::fill_seam_descriptors() {
+    for (DevList<FinRng>* l : {&rng_fin, &rng_fin_kt, &rng_oe}) l->clear();
+    if (!seam_on()) return;
+    auto pair_of = [](const std::vector<int32_t>& tab, size_t i, int32_t (&o)[2]) {
+        o[0] = 2 * i + 1 < tab.size() ? tab[2 * i] : 0;
+        o[1] = 2 * i + 1 < tab.size() ? tab[2 * i + 1] : 0;
+    };
+    auto blocks = [&](const DevList<Tile>& tl, DevList<FinRng>& out) {
+        for (const Tile& t : tl) {
+            FinRng f{};
+            const size_t g = size_t(mats[size_t(t.mat)].group);
+            pair_of(grng_even, g, f.g[0]);
+            pair_of(grng_oe_items, g, f.g[1]);
+            int32_t mr[2];
+            pair_of(mrng_even, size_t(t.mat), mr);
+            f.mb = mr[0];
+            f.me = mr[1];
+            out.push_back(f);
+        }
+    };
+    blocks(tiles_fin, rng_fin);
+    blocks(tiles_fin_kt, rng_fin_kt);
+    blocks(tiles_oe, rng_oe);
 }
 
 void psgd_plan::build_oe() {
@@ -709,6 +737,11 @@ void psgd_plan::layout(int num_tensors) {
         o_gram = scratch(size_t(red_even_cap) * kGramStride * sizeof(double));
         uitems.carve(off, 2 * units_q.size());
     }
+    if (seam_on()) {  // rank-1 plans: the FinRng lists (other plans' carve does not move)
+        rng_fin.carve(off, atleast1(tiles_fin_cap));
+        rng_fin_kt.carve(off, atleast1(tiles_fin_kt_cap));
+        if (oe_ok) rng_oe.carve(off, atleast1(int64_t(tiles_oe.size())));
+    }
     if (wide()) {  // behind everything else: the other plans' carve does not move
         wide_even.carve(off, atleast1(int64_t(wide_even.size())));
         wide_odd.carve(off, atleast1(int64_t(wide_odd.size())));
@@ -731,6 +764,10 @@ int psgd_plan::upload_tiles() const {
     if (int st = upload_all(ws, mats, tiles, tiles_ov, tiles_om, tiles_fin, tiles_fin_kt, segs, wg_seg, red_even,
                             red_odd, grng_even, grng_odd, grng_ss0, mrng_even, uitems))
         return st;
+    if (seam_on())
+        if (int st = upload_all(ws, rng_fin, rng_fin_kt)) return st;
     // (without the odd-even pass its lists are not carved)
+    if (oe_ok && seam_on())
+        if (int st = upload_all(ws, rng_oe)) return st;
     return oe_ok ? upload_all(ws, tiles_oe, red_oe, grng_oe, grng_oe_items) : PSGD_OK;
 }

@@ -110,6 +110,18 @@ struct RedItem {
     int32_t np;      // partials per element
 };
 
+// Rank-1 plans, beside each row block of the fused final passes (tiles_fin, tiles_fin_kt,
+// tiles_oe; same index): the sum-of-squares ranges its prologue sums, copied in from the
+// per-group and per-matrix range tables as Seg copies the matrix fields for k_even, so their
+// loads hang on the block index alone (no MatDesc and range-table round trips before them).
+struct alignas(16) FinRng {
+    int32_t g[2][2];  // the group's sums of squares [begin, end): [0] in the even reduction's
+                      // items (grng_even), [1] in the items after an odd-even pass (grng_oe_items)
+    int32_t mb, me;   // the matrix's even reduction items (rank-1 projection form: c)
+    int32_t pad[2];
+};
+static_assert(sizeof(FinRng) == 32, "FinRng: two 16-byte vectors");
+
 // Orthonormalisation unit: rank 1 -> one shape GROUP (joint norm over count*k values);
 // rank > 1 -> one matrix (Householder QR of a k x r panel).
 struct OrthUnit {
@@ -252,9 +264,12 @@ struct FinalArgs {
     int32_t write_out;    // world size 1: output = sum of all terms
     float* yloc;          // P local -> history
     float* state;         // P local -> reference-visible state buffer
-    // rank-1 fused normalisation of the raw in-factor (as ReduceArgs)
+    // rank-1 fused normalisation of the raw in-factor (as ReduceArgs): per row block its
+    // group's range of `ss_in` is rng[block].g[rsel] (rsel 0: the even reduction's items, 1: the
+    // items after an odd-even pass)
     const float* ss_in;
-    const int32_t* grng_in;
+    const FinRng* rng;
+    int32_t rsel;
     float* xstate;
     float* hx;
     int32_t ntiles;       // row blocks; flat pack items come first (as ApplyArgs)
@@ -262,9 +277,8 @@ struct FinalArgs {
     // projection form (nres = kFinProj, see psgd_final.cuh): P_0 rows and R' per matrix
     const float* proj_p0;  // P layout
     const float* proj_r;   // Q layout: R' (r x r, row-major) at each matrix's qoff
-    // rank-1 projection form: per matrix [begin, end) of the even reduction's sum-of-squares
-    // items (ss_in), for ||Q_0,i||^2 of the matrix against the group norm
-    const int32_t* mrng_in;
+    // (rank-1 projection form: ||Q_0,i||^2 of the matrix against the group norm sums the
+    // matrix's even reduction items, rng[block].mb .. me of ss_in)
     float* xout;           // one-shot exchange: P local also to this rank's exchange slot, or null
     int32_t out_nt;        // output stores nt only (large plans), else write-through (psgd_stream.cuh)
     // odd-even pass (k_final_oe): no residual / output stores; per row block the next (even)

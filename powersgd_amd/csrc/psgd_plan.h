@@ -220,6 +220,11 @@ struct psgd_plan {
     // the K-term form's own row blocks when they differ from the projection form's (MatDesc::
     // fin_rows_kt); empty: the K-term form uses tiles_fin
     DevList<Tile> tiles_fin_kt{"tiles_fin_kt"};
+    // per row block of tiles_fin / tiles_fin_kt / tiles_oe (same index) the sum-of-squares ranges
+    // of its rank-1 prologue (FinRng); rebuilt with the reduction items (fill_seam_descriptors)
+    DevList<FinRng> rng_fin{"rng_fin"}, rng_fin_kt{"rng_fin_kt"}, rng_oe{"rng_oe"};
+    // (they serve the rank-1 norm folds: built, carved and uploaded for rank-1 fp32/bf16 plans only)
+    bool seam_on() const { return rbucket == 1 && dtype != PSGD_F64; }
     // environment knobs, read once at create: PSGD_FUSE_FINAL, PSGD_FIN_PROJ, PSGD_OE (0: that
     // fused form is never used), PSGD_ORTH_CHOL (Cholesky-QR vs Householder)
     bool fuse_final_on = true, fin_proj_on = true, oe_on = true, orth_chol = true;
@@ -366,6 +371,7 @@ struct psgd_plan {
     void set_f64_tiles();
     void set_wide_tiles();
     void build_reduction();
+    void fill_seam_descriptors();  // the FinRng lists, from the range tables
     void set_vec(const std::vector<int>& vec);
     void build_oe();
     void layout(int num_tensors);  // capacities, first tiling, workspace carve (once, at create)

@@ -366,7 +366,8 @@ int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t 
         fa.yloc = p->hist(1, it);
         fa.state = out;
         fa.ss_in = prev_ss;
-        fa.grng_in = prev_grng;
+        fa.rng = p->dev(p->rng_oe);
+        fa.rsel = oe_prev2 ? 1 : 0;  // (an odd iteration) the even items, or the ones after an odd-even pass
         fa.xstate = in;
         fa.hx = p->hist(0, it);
         fa.ntiles = nfin;
@@ -397,7 +398,8 @@ int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t 
         fa.xout = c.xout;
         if (fused) {
             fa.ss_in = prev_ss;  // the in-factor Q came from an even iteration's reduction
-            fa.grng_in = prev_grng;
+            fa.rng = p->dev(own_kt ? p->rng_fin_kt : p->rng_fin) + fr[0];
+            fa.rsel = oe_prev2 ? 1 : 0;
             fa.xstate = in;
             fa.hx = p->hist(0, it);
         }
@@ -405,7 +407,6 @@ int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t 
         if (proj) {  // no error-feedback terms: P_0 and R' only (rank 1: P_0 and the matrix's c)
             fa.proj_p0 = p->hist(0, 0);
             fa.proj_r = p->dev<float>(p->o_rq);
-            fa.mrng_in = p->dev(p->mrng_even);
             fill_terms(p, step, 0, fa.res);
             fa.nres = kFinProj;
         }

@@ -279,24 +279,25 @@ __device__ __forceinline__ float wave_allsum(float v) {
 // Joint norm of a rank-1 group from per-item sums of squares (reference
 // orthogonalization.py:5-6: max(||x||, eps)); every wave that evaluates it uses the same
 // fixed order (lane-strided partial sums, then the DPP/permlane wave tree), so all agree
-// bitwise. Group g's items are grng[2g] .. grng[2g+1].
-__device__ __forceinline__ float group_norm_ss(const float* ss, const int32_t* grng, int group) {
-    const int lane = threadIdx.x & 63;
-    const int b = grng[2 * group], e = grng[2 * group + 1];
-    float acc = 0.f;
-    for (int i = b + lane; i < e; i += 64) acc += ss[i];
-    const float nrm = sqrtf(wave_allsum(acc));
+// bitwise, over the items [b, e) of a group (or of one matrix, for the rank-1 projection form).
+// ss_first / ss_tail: the lane's first term and the remaining ones, so a caller can issue the
+// first loads of several sums together, ahead of other loads, and finish them later.
+__device__ __forceinline__ float ss_first(const float* ss, int b, int e) {
+    const int i = b + int(threadIdx.x & 63);
+    return i < e ? ss[i] : 0.f;
+}
+__device__ __forceinline__ float ss_tail(const float* ss, int b, int e, float acc) {
+    for (int i = b + int(threadIdx.x & 63) + 64; i < e; i += 64) acc += ss[i];
+    return acc;
+}
+__device__ __forceinline__ float norm_floor(float ssq) {
+    const float nrm = sqrtf(ssq);
     return nrm > 1e-16f ? nrm : 1e-16f;
 }
-
-// Plain sum of the sum-of-squares partials [rng[2 i], rng[2 i + 1]) (same wave order as
-// group_norm_ss; one matrix's items for the rank-1 projection form)
-__device__ __forceinline__ float range_ss(const float* ss, const int32_t* rng, int i) {
-    const int lane = threadIdx.x & 63;
-    const int b = rng[2 * i], e = rng[2 * i + 1];
-    float acc = 0.f;
-    for (int k = b + lane; k < e; k += 64) acc += ss[k];
-    return wave_allsum(acc);
+// Group g's items are grng[2g] .. grng[2g+1].
+__device__ __forceinline__ float group_norm_ss(const float* ss, const int32_t* grng, int group) {
+    const int b = grng[2 * group], e = grng[2 * group + 1];
+    return norm_floor(wave_allsum(ss_tail(ss, b, e, ss_first(ss, b, e))));
 }
 
 // One flat-pack item (kFlatItem consecutive elements of one uncompressed tensor; reference

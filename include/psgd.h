@@ -20,6 +20,8 @@
  *   psgd_aggregate_flat    PowerSGD.aggregate           powersgd/powersgd.py:64-74 (world size 1)
  *   psgd_aggregate_comm    PowerSGD.aggregate at world size W over RCCL (:64-74, :204-209)
  *   psgd_aggregate_ipc     the same over IPC exchange buffers with device-side flags (one node)
+ *   psgd_aggregate_mixed   the world-size-1 step on an fp32 residual fed by bf16 gradients, the
+ *                          element-wise passes around the codec folded into it
  *   psgd_runs_*            DDP comm-hook plumbing: a DDP bucket's flat buffer
  *                          <-> the per-parameter tensors, by a run table; the error-feedback add
  *                          the reference gets from autograd's accumulation into p.grad
@@ -352,6 +354,51 @@ int psgd_runs_create_mixed(const int64_t* bucket_off, const int32_t* tensor, con
 int psgd_runs_add_list(psgd_runs* runs, void* const* sources, void* const* tensors, int32_t zero_source,
                        void* stream);
 int psgd_runs_gather_list(psgd_runs* runs, void* const* sources, void* const* tensors, void* stream);
+
+/* ------------------- fp32 error-feedback residual of bf16 gradients, in one call (W = 1) ------ */
+/* The optimizer_step flow with the residual kept in fp32 (powersgd_amd/residual.py) is three
+ * stages: the run-table ADD above (residual += float(g), g = +0.0), psgd_aggregate[_flat] on the
+ * fp32 residual, and the run-table GATHER of the fp32 averages into bf16. psgd_aggregate_mixed is
+ * DEFINED as exactly that sequence, and equals it bit for bit:
+ *   1. residual[i][j] += float(grads_bf16[i][j])   one fp32 add per element
+ *   2. grads_bf16[i][j] = +0.0
+ *   3. psgd_aggregate(plan, residual, avg, step)
+ *   4. out_bf16[j] = bf16(avg[j])                   round to nearest even
+ * but the two element-wise stages run inside the codec's own gradient passes where they can:
+ *   output fold  the step's final pass (k_final_proj / k_final_odd / k_apply) stores its output as
+ *                bf16; the residual stays fp32. Every step of an eligible plan.
+ *   ingest fold  the single-pass k_final_odd (num_iters_per_step = 1 on an odd step, ranks 1 and
+ *                2: the step's only gradient pass) loads residual + float(g) and stores +0.0 to g
+ *                beside its own residual. On every other step the library launches the run-table
+ *                ADD itself, first (the same fold in k_even was measured slower than that ADD and
+ *                is not kept; the odd-even pass and the unfused odd product have none).
+ * `plan`: a bound PSGD_F32 plan driven at world size 1, rank bucket 1, 2 or 4 (largest effective
+ * rank <= 4), one bucket; `residual[i]`: its fp32 tensors (the plan's gradients: alignment as for
+ * psgd_aggregate); `grads_bf16[i]`: the fresh bf16 gradients, the plan's shapes, 2-byte aligned
+ * (8-byte aligned tensors of m % 4 == 0 matrices take vector accesses); `out_bf16`: a dense bf16
+ * buffer, 16-byte aligned, tensor i at element offset psgd_plan_output_offset(i). Any other plan
+ * (rank bucket above 4, wide, fp64 or bf16 dtype, more than one bucket): PSGD_ERR_VALUE before
+ * anything is launched, and psgd_plan_mixed_folds reports 0 / 0.
+ * Every mixed kernel instance is admitted like the fused final pass (at least two waves per SIMD,
+ * no scratch; asked of the runtime). Without an admitted ingest instance that fold is dropped (the
+ * ADD launch takes its place); a plan whose final pass has no admitted bf16-output instance is
+ * ineligible (there is no fp32 output buffer to fall back to).
+ * psgd_plan_mixed_folds: which folds `step` takes (1 / 0 each). On an unbound plan the answer is
+ * this build's on the current device (0 / 0 without one).
+ * psgd_aggregate_mixed_flat: with the uncompressed tensors of psgd_aggregate_flat riding in the
+ * final launch: `flat` an fp32 flat plan over their fp32 residual tensors `unc_residual`,
+ * `unc_bf16` their bf16 gradients, `flat_out_bf16` the dense bf16 flat buffer: per element
+ * flat = bf16(x + float(g)), x = +0.0, g = +0.0 (the ADD, the flat pack and the GATHER of the
+ * three-stage flow). flat null or empty: psgd_aggregate_mixed.
+ * The first mixed call (or fold query) of a bound plan makes one small device allocation owned by
+ * the plan (pointer tables of the bf16 gradients, the ADD's run items), freed with the plan; the
+ * caller's workspace layout is untouched. */
+int psgd_aggregate_mixed(psgd_plan* plan, void* const* grads_bf16, void* const* residual,
+                         void* out_bf16, int64_t step, void* stream);
+int psgd_aggregate_mixed_flat(psgd_plan* plan, void* const* grads_bf16, void* const* residual,
+                              void* out_bf16, int64_t step, psgd_flat* flat, void* const* unc_bf16,
+                              void* const* unc_residual, void* flat_out_bf16, void* stream);
+int psgd_plan_mixed_folds(const psgd_plan* plan, int64_t step, int32_t* fold_in, int32_t* fold_out);
 
 #ifdef __cplusplus
 }

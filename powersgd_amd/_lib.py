@@ -77,6 +77,9 @@ _SIGNATURES = {
                                 ctypes.POINTER(_vp)], _i32),
     "psgd_runs_add_list": ([_vp, _vp, _vp, _i32, _vp], _i32),
     "psgd_runs_gather_list": ([_vp, _vp, _vp, _vp], _i32),
+    "psgd_aggregate_mixed": ([_vp, _vp, _vp, _vp, _i64, _vp], _i32),
+    "psgd_aggregate_mixed_flat": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_mixed_folds": ([_vp, _i64, _P_i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -212,6 +215,25 @@ class Plan:
     def aggregate_flat(self, grads, out_ptr: int, step: int, flat: "FlatPlan", unc, flat_out: int,
                        stream: int) -> None:
         check(lib().psgd_aggregate_flat(self._h, grads, out_ptr, step, flat._h, unc, flat_out, stream))
+
+    # --- fp32 residual of bf16 gradients: the world-size-1 step with the ADD / GATHER passes folded
+    def mixed_folds(self, step: int):
+        """(fold_in, fold_out) of ``step`` under ``aggregate_mixed`` (psgd_plan_mixed_folds): 1 where
+        the ingest of the bf16 gradients / the bf16 rounding of the output runs inside the codec's
+        own gradient pass; (0, 0) for a plan ``aggregate_mixed`` refuses."""
+        fi, fo = _i32(), _i32()
+        check(lib().psgd_plan_mixed_folds(self._h, step, ctypes.byref(fi), ctypes.byref(fo)))
+        return int(fi.value), int(fo.value)
+
+    def aggregate_mixed(self, grads_bf16, residual, out_ptr: int, step: int, stream: int, flat=None, unc_bf16=None,
+                        unc_residual=None, flat_out: int = 0) -> None:
+        """psgd_aggregate_mixed (``flat`` given: psgd_aggregate_mixed_flat). Raises ``ValueError`` for
+        a plan it does not serve, before anything is launched."""
+        if flat is None:
+            check(lib().psgd_aggregate_mixed(self._h, grads_bf16, residual, out_ptr, step, stream))
+        else:
+            check(lib().psgd_aggregate_mixed_flat(self._h, grads_bf16, residual, out_ptr, step, flat._h, unc_bf16,
+                                                  unc_residual, flat_out, stream))
 
     # --- buckets of shape groups (W > 1 comm/compute overlap)
     def set_buckets(self, group_end: Sequence[int]) -> None:

@@ -19,6 +19,8 @@
 // collective, :204-219): writes the output, reads no gradient.
 #pragma once
 
+#include <type_traits>
+
 #include "psgd_stream.cuh"
 
 namespace psgd {
@@ -122,10 +124,18 @@ constexpr int kProjRows = kFinRowsMax;
 // product: column partials sum_rows (g - P x^T) P over the row block (reference :185-202 for
 // iteration k + 1 with its in-factor P_k before the joint norm, which the reduction divides
 // out), and sum_rows P^2 for that norm. The gradient is read once for both iterations.
-template <typename T, int R, int K, int SMAX, bool VEC, int NT, int RB, bool PJ = false, bool OE = false>
+// TO / IN (psgd_aggregate_mixed, MixArgs): TO is the output's element type (the gradient's; bf16
+// over an fp32 residual in the mixed instances). IN, the ingest fold of the single-pass form (K =
+// 0): the row is G_0 + float(src) with src the bf16 gradient `gsrc` of this matrix (one fp32 add
+// per element, the run-table ADD pass), and +0.0 goes back to src beside the residual stores; src
+// is 2-byte aligned: 8-byte vector accesses when it is 8-byte aligned and VEC, else element ones.
+template <typename T, int R, int K, int SMAX, bool VEC, int NT, int RB, bool PJ = false, bool OE = false,
+          typename TO = T, bool IN = false>
 __device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc& d, const Tile& t, const FinSs& fs,
-                                               float* red, float* rqs = nullptr, float* oered = nullptr) {
+                                               float* red, float* rqs = nullptr, float* oered = nullptr,
+                                               const void* gsrc = nullptr) {
     static_assert(!OE || (R == 1 && !PJ), "the odd-even pass is rank 1, K-term form");
+    static_assert(!IN || (K == 0 && !PJ && !OE), "the ingest fold is built for the single-pass K-term form");
     constexpr int KC = K > 0 ? K : 1;
     constexpr int NW = NT / 64;
     const int r = d.r;
@@ -140,8 +150,12 @@ __device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc
     const int nres = K >= 0 ? K : a.nres;
     const uint32_t nbytes = uint32_t(d.n * d.m * int64_t(sizeof(T)));
     const rsrc_t gs = __builtin_amdgcn_make_buffer_rsrc(a.grads[t.tensor], 0, int(nbytes), 0x00020000);
-    const rsrc_t os = __builtin_amdgcn_make_buffer_rsrc(static_cast<T*>(a.out) + d.out_off, 0, int(nbytes),
-                                                        0x00020000);
+    const rsrc_t os = __builtin_amdgcn_make_buffer_rsrc(static_cast<TO*>(a.out) + d.out_off, 0,
+                                                        int(uint32_t(d.n * d.m * int64_t(sizeof(TO)))), 0x00020000);
+    // IN: the bf16 gradients of this matrix (same element offsets as gs)
+    const rsrc_t is = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(IN ? gsrc : nullptr), 0,
+                                                        int(IN ? uint32_t(d.n * d.m * 2) : 0u), 0x00020000);
+    const bool ivec = IN && VEC && (reinterpret_cast<uintptr_t>(gsrc) & 7) == 0;
     const gptr<const float> X = gconst<float>(a.x) + d.qoff;
 
     int32_t ccol[SMAX];
@@ -156,10 +170,14 @@ __device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc
     // Every load of a batch is issued unconditionally (rows past the block end and
     // segments past the row end load 0 through kOob / clamped factor rows), so the number
     // of loads in flight is the same on every path and the waits stay counted, not full
-    struct Batch {
+    struct BatchG {
         float g[RB][SMAX][4];
         float ap[KC][RB][R];
     };
+    struct BatchIn : BatchG {
+        float h[RB][SMAX][4];  // IN: float(src) of the same elements
+    };
+    using Batch = typename std::conditional<IN, BatchIn, BatchG>::type;
     auto load = [&](Batch& bt, int b) {
         const int64_t ib = row0 + (int64_t(b) * RGS + rg) * RB;
 #pragma unroll
@@ -168,6 +186,16 @@ __device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc
 #pragma unroll
             for (int s = 0; s < SMAX; ++s)
                 fin_ld<T, VEC>(gs, rowe + uint32_t(ccol[s]), act[s] && ib + u < row_end, ccol[s], m, bt.g[u][s]);
+            if constexpr (IN) {
+#pragma unroll
+                for (int s = 0; s < SMAX; ++s) {
+                    const bool ok = act[s] && ib + u < row_end;
+                    if (ivec)
+                        fin_ld<bf16_t, true>(is, rowe + uint32_t(ccol[s]), ok, ccol[s], m, bt.h[u][s]);
+                    else
+                        fin_ld<bf16_t, false>(is, rowe + uint32_t(ccol[s]), ok, ccol[s], m, bt.h[u][s]);
+                }
+            }
         }
         if constexpr (K > 0) {
 #pragma unroll
@@ -327,6 +355,15 @@ __device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc
             for (int s = 0; s < SMAX; ++s)
 #pragma unroll
                 for (int v = 0; v < 4; ++v) keep(g[u][s][v]);
+            if constexpr (IN) {  // residual + fresh gradient: one fp32 add per element
+#pragma unroll
+                for (int s = 0; s < SMAX; ++s)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        keep(bt.h[u][s][v]);
+                        g[u][s][v] = g[u][s][v] + bt.h[u][s][v];
+                    }
+            }
 #pragma unroll
             for (int c = 0; c < R; ++c) dot[u][c] = 0.f;
 #pragma unroll
@@ -476,11 +513,18 @@ __device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc
                     }
                     const bool ok = valid && act[s];
                     fin_st<T, VEC>(gs, rowe + uint32_t(ccol[s]), ok, ccol[s], m, res);
+                    if constexpr (IN) {  // the gradients are consumed in the pass that reads them
+                        const float z[4] = {0.f, 0.f, 0.f, 0.f};
+                        if (ivec)
+                            fin_st<bf16_t, true>(is, rowe + uint32_t(ccol[s]), ok, ccol[s], m, z);
+                        else
+                            fin_st<bf16_t, false>(is, rowe + uint32_t(ccol[s]), ok, ccol[s], m, z);
+                    }
                     if (PJ || a.write_out) {
                         if (a.out_nt)
-                            fin_st<T, VEC, kStAuxOutNt>(os, rowe + uint32_t(ccol[s]), ok, ccol[s], m, o);
+                            fin_st<TO, VEC, kStAuxOutNt>(os, rowe + uint32_t(ccol[s]), ok, ccol[s], m, o);
                         else
-                            fin_st<T, VEC>(os, rowe + uint32_t(ccol[s]), ok, ccol[s], m, o);
+                            fin_st<TO, VEC>(os, rowe + uint32_t(ccol[s]), ok, ccol[s], m, o);
                     }
                 }
             }
@@ -525,8 +569,8 @@ __device__ __forceinline__ void final_odd_tile(const FinalArgs& a, const MatDesc
     }
 }
 
-template <typename T, int R, int K, int SMAX, bool PJ = false>
-__device__ __forceinline__ void final_odd_block(const FinalArgs& a) {
+template <typename T, int R, int K, int SMAX, bool PJ = false, typename TO = T, bool IN = false>
+__device__ __forceinline__ void final_odd_block(const FinalArgs& a, const MixArgs* mx = nullptr) {
     constexpr int NT = FinNT<R>::value, RB = FinRB<R>::value;
     // batch row sums (2 buffers)
     constexpr int kRed = 2 * (NT / 64) * RB * R;
@@ -535,17 +579,23 @@ __device__ __forceinline__ void final_odd_block(const FinalArgs& a) {
     // blocks [0, nitems): uncompressed tensors (first: beside the first wave of row blocks,
     // not in the launch tail); then the row blocks
     const int nf = a.flat.nitems;
+    constexpr bool MIX = !std::is_same<TO, T>::value;  // the mixed instances (MixArgs)
     if (int(blockIdx.x) < nf) {
-        flat_pack_item<T, NT>(a.flat, blockIdx.x);
+        if constexpr (MIX)
+            flat_mix_item<NT>(a.flat, mx->unc_src, blockIdx.x);
+        else
+            flat_pack_item<T, NT>(a.flat, blockIdx.x);
         return;
     }
     const Tile t = a.tiles[blockIdx.x - nf];
     const FinSs fs = fin_ss_begin<R, PJ>(a, blockIdx.x - nf);  // beside the tile: no MatDesc hop
+    const void* gsrc = nullptr;
+    if constexpr (IN) gsrc = mx->src[t.tensor];  // beside the MatDesc load
     const MatDesc d = a.mats[t.mat];
     if (d.vec)
-        final_odd_tile<T, R, K, SMAX, true, NT, RB, PJ>(a, d, t, fs, red, rqs);
+        final_odd_tile<T, R, K, SMAX, true, NT, RB, PJ, false, TO, IN>(a, d, t, fs, red, rqs, nullptr, gsrc);
     else
-        final_odd_tile<T, R, K, SMAX, false, NT, RB, PJ>(a, d, t, fs, red, rqs);
+        final_odd_tile<T, R, K, SMAX, false, NT, RB, PJ, false, TO, IN>(a, d, t, fs, red, rqs, nullptr, gsrc);
 }
 
 template <typename T, int R, int K, int SMAX>
@@ -578,6 +628,19 @@ template <typename T, int R, int SMAX>
 __global__ __launch_bounds__(FinNT<R>::value) __attribute__((amdgpu_waves_per_eu(R == 4 ? PSGD_PROJ4_WPE : R == 1 ? PSGD_PROJ1_WPE : 1))) void k_final_proj(
     FinalArgs a) {
     final_odd_block<T, R, 0, SMAX, true>(a);
+}
+
+// The mixed instances (psgd_aggregate_mixed, MixArgs): the fp32 forms above with the output stored
+// as bf16 and the flat items as flat_mix_item; IN: the single-pass form (K = 0) also ingests the
+// bf16 gradients. Same launch bounds and occupancy targets as their fp32 forms.
+template <int R, int K, int SMAX, bool IN>
+__global__ __launch_bounds__(FinNT<R>::value) void k_final_odd_mix(FinalArgs a, MixArgs x) {
+    final_odd_block<float, R, K, SMAX, false, bf16_pin_t, IN>(a, &x);
+}
+template <int R, int SMAX>
+__global__ __launch_bounds__(FinNT<R>::value) __attribute__((amdgpu_waves_per_eu(R == 4 ? PSGD_PROJ4_WPE : R == 1 ? PSGD_PROJ1_WPE : 1))) void k_final_proj_mix(
+    FinalArgs a, MixArgs x) {
+    final_odd_block<float, R, 0, SMAX, true, bf16_pin_t, false>(a, &x);
 }
 
 // output = sum_k alpha * (A_k B_k^T) on the lane-column tiles (same order as k_apply's
@@ -679,12 +742,20 @@ __global__ __launch_bounds__(kBlock) void k_lowrank_out(ApplyArgs a) {
 // SMAX (register segments) is the smallest instantiated bucket >= the plan's max fin_S.
 // ntiles == 0: no launch; `*waves` (if non-null) receives the resident waves per SIMD of
 // the instance that would run (the plan only fuses at >= 2).
-template <typename T, int R, int SMAX, int K, bool PJ = false>
-hipError_t launch_final_k(const FinalArgs& a, int ntiles, hipStream_t s, int* waves) {
+// MIX (with `mx`): 0 the gradient type's own instance; 1 / 2 the mixed instance of an fp32 plan
+// (bf16 output; 2: with the ingest fold, K = 0 only)
+template <typename T, int R, int SMAX, int K, bool PJ = false, int MIX = 0>
+hipError_t launch_final_k(const FinalArgs& a, int ntiles, hipStream_t s, int* waves, const MixArgs* mx = nullptr) {
     constexpr int NT = FinNT<R>::value;
+    static_assert(MIX == 0 || std::is_same<T, float>::value, "mixed instances: fp32 plans");
+    static_assert(MIX != 2 || (K == 0 && !PJ), "ingest fold: the single-pass form");
     if (waves) {  // resident waves per SIMD; 0 when the instance spills to scratch
         const void* fn;
-        if constexpr (PJ)
+        if constexpr (MIX != 0 && PJ)
+            fn = reinterpret_cast<const void*>(&k_final_proj_mix<R, SMAX>);
+        else if constexpr (MIX != 0)
+            fn = reinterpret_cast<const void*>(&k_final_odd_mix<R, K, SMAX, MIX == 2>);
+        else if constexpr (PJ)
             fn = reinterpret_cast<const void*>(&k_final_proj<T, R, SMAX>);
         else
             fn = reinterpret_cast<const void*>(&k_final_odd<T, R, K, SMAX>);
@@ -696,7 +767,11 @@ hipError_t launch_final_k(const FinalArgs& a, int ntiles, hipStream_t s, int* wa
         *waves = fa.localSizeBytes > 0 ? 0 : blocks * (NT / 64) / 4;
     }
     if (ntiles == 0) return hipSuccess;
-    if constexpr (PJ)
+    if constexpr (MIX != 0 && PJ)
+        timed_launch(&k_final_proj_mix<R, SMAX>, dim3(ntiles + a.flat.nitems), dim3(NT), s, a, *mx);
+    else if constexpr (MIX != 0)
+        timed_launch(&k_final_odd_mix<R, K, SMAX, MIX == 2>, dim3(ntiles + a.flat.nitems), dim3(NT), s, a, *mx);
+    else if constexpr (PJ)
         timed_launch(&k_final_proj<T, R, SMAX>, dim3(ntiles + a.flat.nitems), dim3(NT), s, a);
     else
         timed_launch(&k_final_odd<T, R, K, SMAX>, dim3(ntiles + a.flat.nitems), dim3(NT), s, a);
@@ -707,55 +782,66 @@ hipError_t launch_final_k(const FinalArgs& a, int ntiles, hipStream_t s, int* wa
 // e.g. the 4-iteration LSTM config); otherwise read per use from L1/L2 (K = -1).
 // ntiles == 0: no launch; `*waves` (if non-null) receives the resident waves per SIMD of
 // the instance that would run (the plan only fuses at >= 2).
-template <typename T, int R, int SMAX>
-hipError_t dispatch_final_k(int nres, const FinalArgs& a, int ntiles, hipStream_t s, int* waves) {
-    if (nres == kFinProj) return launch_final_k<T, R, SMAX, 0, true>(a, ntiles, s, waves);
-    if constexpr (R == 4) {
-        return hipErrorInvalidValue;  // rank 4: the projection form only (psgd_plan.cpp, set_vec)
+template <typename T, int R, int SMAX, int MIX = 0>
+hipError_t dispatch_final_k(int nres, const FinalArgs& a, int ntiles, hipStream_t s, int* waves,
+                            const MixArgs* mx = nullptr) {
+    if constexpr (MIX == 2) {  // ingest fold: the single-pass K-term form only
+        if constexpr (R == 4) return hipErrorInvalidValue;
+        else return nres == 0 ? launch_final_k<T, R, SMAX, 0, false, 2>(a, ntiles, s, waves, mx) : hipErrorInvalidValue;
     } else {
-        switch (nres) {
-            case 0: return launch_final_k<T, R, SMAX, 0>(a, ntiles, s, waves);
-            case 1: return launch_final_k<T, R, SMAX, 1>(a, ntiles, s, waves);
-            case 2:
-                if constexpr (SMAX <= 3) return launch_final_k<T, R, SMAX, 2>(a, ntiles, s, waves);
-                break;
-            case 3:
-                if constexpr (SMAX <= 3) return launch_final_k<T, R, SMAX, 3>(a, ntiles, s, waves);
-                break;
-            default: break;
+        if (nres == kFinProj) return launch_final_k<T, R, SMAX, 0, true, MIX>(a, ntiles, s, waves, mx);
+        if constexpr (R == 4) {
+            return hipErrorInvalidValue;  // rank 4: the projection form only (psgd_plan.cpp, set_vec)
+        } else {
+            switch (nres) {
+                case 0: return launch_final_k<T, R, SMAX, 0, false, MIX>(a, ntiles, s, waves, mx);
+                case 1: return launch_final_k<T, R, SMAX, 1, false, MIX>(a, ntiles, s, waves, mx);
+                case 2:
+                    if constexpr (SMAX <= 3) return launch_final_k<T, R, SMAX, 2, false, MIX>(a, ntiles, s, waves, mx);
+                    break;
+                case 3:
+                    if constexpr (SMAX <= 3) return launch_final_k<T, R, SMAX, 3, false, MIX>(a, ntiles, s, waves, mx);
+                    break;
+                default: break;
+            }
+            return launch_final_k<T, R, SMAX, -1, false, MIX>(a, ntiles, s, waves, mx);
         }
-        return launch_final_k<T, R, SMAX, -1>(a, ntiles, s, waves);
     }
 }
 
 // Instantiated (R, SMAX) pairs: the ones that can keep two waves per SIMD without scratch
 // (tools/regs.py); any other request returns hipErrorInvalidValue and the plan keeps the
 // unfused final iteration.
-template <typename T, int R>
-hipError_t dispatch_final_r(int nres, int smax, const FinalArgs& a, int ntiles, hipStream_t s, int* waves) {
-    if (smax <= 2) return dispatch_final_k<T, R, 2>(nres, a, ntiles, s, waves);
-    if (smax <= 3) return dispatch_final_k<T, R, 3>(nres, a, ntiles, s, waves);
-    if constexpr (R == 4 && PSGD_FIN_NT4 == 256) {
-        if (smax <= 5 && nres == kFinProj) return launch_final_k<T, R, 5, 0, true>(a, ntiles, s, waves);
+template <typename T, int R, int MIX = 0>
+hipError_t dispatch_final_r(int nres, int smax, const FinalArgs& a, int ntiles, hipStream_t s, int* waves,
+                            const MixArgs* mx = nullptr) {
+    if (smax <= 2) return dispatch_final_k<T, R, 2, MIX>(nres, a, ntiles, s, waves, mx);
+    if (smax <= 3) return dispatch_final_k<T, R, 3, MIX>(nres, a, ntiles, s, waves, mx);
+    if constexpr (R == 4 && PSGD_FIN_NT4 == 256 && MIX != 2) {
+        if (smax <= 5 && nres == kFinProj) return launch_final_k<T, R, 5, 0, true, MIX>(a, ntiles, s, waves, mx);
     }
     if constexpr (R <= 2) {
-        if (smax <= 5) return dispatch_final_k<T, R, 5>(nres, a, ntiles, s, waves);
+        if (smax <= 5) return dispatch_final_k<T, R, 5, MIX>(nres, a, ntiles, s, waves, mx);
         if (smax <= 12 && (nres <= 1 || nres == kFinProj)) {
-            if (nres == kFinProj) return launch_final_k<T, R, 12, 0, true>(a, ntiles, s, waves);
-            return nres == 0 ? launch_final_k<T, R, 12, 0>(a, ntiles, s, waves)
-                             : launch_final_k<T, R, 12, 1>(a, ntiles, s, waves);
+            if constexpr (MIX == 2) {
+                return nres == 0 ? launch_final_k<T, R, 12, 0, false, 2>(a, ntiles, s, waves, mx) : hipErrorInvalidValue;
+            } else {
+                if (nres == kFinProj) return launch_final_k<T, R, 12, 0, true, MIX>(a, ntiles, s, waves, mx);
+                return nres == 0 ? launch_final_k<T, R, 12, 0, false, MIX>(a, ntiles, s, waves, mx)
+                                 : launch_final_k<T, R, 12, 1, false, MIX>(a, ntiles, s, waves, mx);
+            }
         }
     }
     return hipErrorInvalidValue;
 }
 
-template <typename T>
+template <typename T, int MIX = 0>
 hipError_t dispatch_final(int R, int nres, int smax, const FinalArgs& a, int ntiles, hipStream_t s,
-                          int* waves) {
+                          int* waves, const MixArgs* mx = nullptr) {
     switch (R) {
-        case 1: return dispatch_final_r<T, 1>(nres, smax, a, ntiles, s, waves);
-        case 2: return dispatch_final_r<T, 2>(nres, smax, a, ntiles, s, waves);
-        case 4: return dispatch_final_r<T, 4>(nres, smax, a, ntiles, s, waves);
+        case 1: return dispatch_final_r<T, 1, MIX>(nres, smax, a, ntiles, s, waves, mx);
+        case 2: return dispatch_final_r<T, 2, MIX>(nres, smax, a, ntiles, s, waves, mx);
+        case 4: return dispatch_final_r<T, 4, MIX>(nres, smax, a, ntiles, s, waves, mx);
         default: return hipErrorInvalidValue;
     }
 }

@@ -451,6 +451,29 @@ struct RunsMixArgs {
 };
 hipError_t launch_runs_mix(int bucket_dtype, int tensor_dtype, int mode, const RunsMixArgs& a, hipStream_t s);
 
+// psgd_aggregate_mixed (fp32 plans at world size 1, rank buckets 1 / 2 / 4): the fp32 codec on an
+// fp32 error-feedback residual fed by bf16 gradients, with the two element-wise passes around it
+// folded into its own gradient passes. The mixed kernel instances take this second argument
+// beside the codec's own (whose structs, and so every other instance, stay as they are):
+//   output fold   the step's final pass (k_final_odd / k_final_proj / k_apply) stores its output
+//                 as bf16 (StIo<bf16_t>; `out` and the flat buffer are bf16 buffers); the residual
+//                 stays fp32
+//   ingest fold   the single-pass k_final_odd (I = 1, odd step: the step's only gradient pass)
+//                 loads residual + float(src) (ONE fp32 add) and stores +0.0 to src beside its own
+//                 residual. (The same fold in k_even was built and measured slower than the
+//                 run-table ADD it replaces, DESIGN.md section 10: not kept.)
+//   flat items    an uncompressed tensor's item does both: flat = bf16(x + float(src)), x = src = +0.0
+struct MixArgs {
+    void* const* src;      // bf16 gradients of the plan's tensors (gradient-table order), ingest fold
+    void* const* unc_src;  // bf16 gradients of the uncompressed tensors (the flat plan's order)
+};
+// psgd_mixed_{final,apply}.hip. ntiles == 0: no launch; `*waves` (if non-null) receives
+// the resident waves per SIMD of the instance that would run, 0 when it uses scratch.
+hipError_t launch_final_mix(int R, int nres, int smax, bool ingest, const FinalArgs& a, const MixArgs& x, int ntiles,
+                            hipStream_t s, int* waves);
+hipError_t launch_apply_mix(int R, int nterms, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s,
+                            int* waves);
+
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),
 // then two parities x iterations slots of xchg_slot floats each; the producer kernels (k_reduce,

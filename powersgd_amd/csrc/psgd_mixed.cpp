@@ -1,0 +1,215 @@
+// psgd_aggregate_mixed / psgd_aggregate_mixed_flat / psgd_plan_mixed_folds (include/psgd.h): the
+// world-size-1 step of an fp32 plan on an fp32 error-feedback residual fed by bf16 gradients, with
+// the element-wise passes around the codec folded into its own gradient passes (MixArgs,
+// psgd_internal.h). Defined as, and bit for bit equal to,
+//   residual += float(g); g = +0.0        (psgd_runs_add_list, zero_source)
+//   psgd_aggregate[_flat] on the residual
+//   out = bf16(averages)                  (psgd_runs_gather)
+// Which passes fold on a step:
+//   output fold  always (the plan is eligible only when the final pass of either step parity has
+//                an admitted mixed instance: there is no fp32 output buffer to fall back to)
+//   ingest fold  when the step's only gradient pass is the single-pass k_final_odd (I = 1, odd
+//                step, ranks 1 / 2) and that mixed instance is admitted; every other step runs the
+//                run-table ADD as a launch of its own first (first pass k_even: the fold was built
+//                and measured slower than the ADD it replaces; k_final_oe
+//                and the unfused odd product: no fold built)
+#include <memory>
+
+#include "psgd_plan.h"
+
+namespace {
+
+// rank buckets 1 / 2 / 4, fp32, not wide, one bucket
+const char* ineligible(const psgd_plan* p) {
+    if (p->dtype != PSGD_F32) return "psgd_aggregate_mixed takes an fp32 plan (the fp32 residual of bf16 gradients)";
+    if (p->wide() || p->rbucket > 4) return "psgd_aggregate_mixed serves rank buckets 1, 2 and 4";
+    if (p->spans.size() > 1) return "psgd_aggregate_mixed takes a plan of one bucket";
+    return nullptr;
+}
+
+bool admitted(hipError_t e, int waves) { return e == hipSuccess && waves >= 2; }
+
+// (Re-)ask the runtime about the mixed instances this plan's current tiling would launch
+void admit(psgd_plan* p) {
+    psgd_plan::Mixed& m = *p->mixed;
+    const uint64_t key = uint64_t(p->fin_ok) | uint64_t(p->fin_proj) << 1 | uint64_t(p->oe_ok) << 2 |
+                         uint64_t(uint32_t(p->fin_smax)) << 8 | uint64_t(uint32_t(p->out_nt)) << 40;
+    if (m.key == key) return;
+    m.key = key;
+    const MixArgs none{};
+    int w = 0;
+    const int smax = fin_bucket(p->fin_smax);
+    m.fin_in = false;
+    if (p->mix_ingest_on && p->iters == 1 && p->fused_final(1, true) && smax > 0) {
+        w = 0;
+        m.fin_in = admitted(launch_final_mix(p->rbucket, 0, smax, true, FinalArgs{}, none, 0, nullptr, &w), w);
+    }
+    for (int par = 0; par < 2; ++par) {  // the final pass of a step of this parity
+        w = 0;
+        if (p->fused_final(par, true)) {
+            const int nres = p->proj_final(par, true) ? kFinProj : p->iters - 1;
+            m.out[par] = smax > 0 && admitted(launch_final_mix(p->rbucket, nres, smax, false, FinalArgs{}, none, 0, nullptr, &w), w);
+        } else {
+            ApplyArgs aa{};
+            aa.out_nt = p->out_nt;
+            m.out[par] = admitted(launch_apply_mix(p->rbucket, p->iters, aa, none, 0, nullptr, &w), w);
+        }
+    }
+}
+
+// The plan's mixed state: the bf16 gradients' pointer tables and the run-table ADD, device side in
+// one allocation of the plan's own (made once, by the first call on a bound plan)
+int ensure(psgd_plan* p) {
+    if (p->mixed) return PSGD_OK;
+    std::unique_ptr<psgd_plan::Mixed> m(new psgd_plan::Mixed());
+    const size_t nt = p->shapes.size();
+    std::vector<int64_t> zero(nt, 0), numel(nt, 1);
+    std::vector<int32_t> idx(nt);
+    for (size_t i = 0; i < nt; ++i) {
+        idx[i] = int32_t(i);
+        for (int64_t x : p->shapes[i]) numel[i] *= x;
+    }
+    p->mixed = m.release();
+    psgd_plan::Mixed& mx = *p->mixed;
+    if (int st = psgd_runs_create_mixed(zero.data(), idx.data(), zero.data(), numel.data(), idx.data(), int32_t(nt),
+                                        int32_t(nt), int32_t(nt), PSGD_BF16, PSGD_F32, &mx.add))
+        return st;
+    int64_t rb = 0;
+    if (int st = psgd_runs_workspace_bytes(mx.add, &rb)) return st;
+    const size_t tab = align256(TableCache::bytes(nt));
+    PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&mx.dev), tab + size_t(rb)));
+    mx.add_ws = mx.dev + tab;
+    mx.src_tab.bind(mx.dev, nt);
+    return psgd_runs_bind(mx.add, p->device, mx.add_ws);
+}
+
+void folds_at(const psgd_plan* p, int64_t step, int32_t* in, int32_t* out) {
+    const psgd_plan::Mixed& m = *p->mixed;
+    const bool eligible = m.out[0] && m.out[1];
+    const bool single = p->iters == 1 && !p->even(step, 0) && p->fused_final(step, true);
+    *out = eligible ? 1 : 0;
+    *in = eligible && single && m.fin_in ? 1 : 0;
+}
+
+int mixed_impl(psgd_plan* p, void* const* grads, void* const* residual, void* out, int64_t step, psgd_flat* f,
+               void* const* unc, void* const* unc_residual, void* flat_out, hipStream_t s) {
+    if (const char* why = ineligible(p)) return fail(PSGD_ERR_VALUE, why);
+    const size_t nt = p->shapes.size();
+    for (size_t i = 0; i < nt; ++i) {
+        if (!grads[i] || !residual[i]) return fail(PSGD_ERR_VALUE, "null gradient pointer");
+        if (reinterpret_cast<uintptr_t>(grads[i]) % 2) return fail(PSGD_ERR_LAYOUT, "bf16 gradients must be 2-byte aligned");
+        if (reinterpret_cast<uintptr_t>(residual[i]) % 4) return fail(PSGD_ERR_LAYOUT, "the fp32 residual must be 4-byte aligned");
+    }
+    DevScope scope(p->device);
+    if (int st = ensure(p)) return st;
+    psgd_plan::Mixed& m = *p->mixed;
+    // the tiling the step will run on (the residual's alignment decides the vector layout)
+    if (int st = refresh_pointers(p, residual, s)) return st;
+    admit(p);
+    int32_t in = 0, fo = 0;
+    folds_at(p, step, &in, &fo);
+    if (!fo)
+        return fail(PSGD_ERR_VALUE, "psgd_aggregate_mixed: no admitted bf16-output instance of this plan's final pass "
+                                    "(two waves per SIMD, no scratch)");
+    FlatArgs fa{};
+    MixArgs x{};
+    if (f) {
+        if (size_t(f->count) > m.unc_cap) {  // (first call, or a larger flat plan than the last one's)
+            PSGD_HIP(hipStreamSynchronize(s));
+            m.unc_tab.release();
+            if (m.unc_dev) PSGD_HIP(hipFree(m.unc_dev));
+            m.unc_dev = nullptr;
+            PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&m.unc_dev), TableCache::bytes(size_t(f->count))));
+            m.unc_cap = size_t(f->count);
+            m.unc_tab.bind(m.unc_dev, size_t(f->count));
+        } else if (m.unc_tab.n != size_t(f->count)) {
+            PSGD_HIP(hipStreamSynchronize(s));
+            m.unc_tab.bind(m.unc_dev, size_t(f->count));
+        }
+        for (int32_t i = 0; i < f->count; ++i)
+            if (!unc[i] || !unc_residual[i]) return fail(PSGD_ERR_VALUE, "null uncompressed tensor pointer");
+        if (int st = flat_args(f, unc_residual, flat_out, 1, s, &fa)) return st;
+        PSGD_HIP(m.unc_tab.select(unc, s));
+        x.unc_src = m.unc_tab.table();
+    }
+    if (in) {
+        PSGD_HIP(m.src_tab.select(grads, s));
+        x.src = m.src_tab.table();
+    } else {
+        if (int st = psgd_runs_add_list(m.add, grads, residual, 1, s)) return st;
+    }
+    StepCtx c;
+    c.fl = f ? &fa : nullptr;
+    c.out = out;
+    c.mix = &x;
+    c.mix_in = in != 0;
+    return aggregate_ctx(p, residual, step, s, c);
+}
+
+}  // namespace
+
+void psgd::mixed_release(psgd_plan* p) {
+    if (!p->mixed) return;
+    psgd_plan::Mixed* m = p->mixed;
+    m->src_tab.release();
+    m->unc_tab.release();
+    if (m->add) (void)psgd_runs_destroy(m->add);
+    if (m->dev) (void)hipFree(m->dev);
+    if (m->unc_dev) (void)hipFree(m->unc_dev);
+    delete m;
+    p->mixed = nullptr;
+}
+
+extern "C" {
+
+int psgd_plan_mixed_folds(const psgd_plan* plan, int64_t step, int32_t* fold_in, int32_t* fold_out) {
+    if (!plan || !fold_in || !fold_out) return fail(PSGD_ERR_VALUE, "null argument");
+    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
+    *fold_in = *fold_out = 0;
+    if (ineligible(plan)) return PSGD_OK;
+    // admission is a property of this build's kernels on the device (asked once per tiling); the
+    // query caches it in the plan like the first mixed call does
+    psgd_plan* p = const_cast<psgd_plan*>(plan);
+    DevScope scope(p->device);
+    if (!p->mixed) {
+        if (!p->bound) {  // no device yet: ask without keeping device state
+            psgd_plan::Mixed tmp;
+            p->mixed = &tmp;
+            admit(p);
+            folds_at(p, step, fold_in, fold_out);
+            p->mixed = nullptr;
+            return PSGD_OK;
+        }
+        if (int st = ensure(p)) return st;
+    }
+    admit(p);
+    folds_at(p, step, fold_in, fold_out);
+    return PSGD_OK;
+}
+
+int psgd_aggregate_mixed_flat(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,
+                              psgd_flat* f, void* const* unc_bf16, void* const* unc_residual, void* flat_out_bf16,
+                              void* stream) {
+    if (!p || !grads_bf16 || !residual || !out_bf16) return fail(PSGD_ERR_VALUE, "null argument");
+    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
+    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
+    if (reinterpret_cast<uintptr_t>(out_bf16) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    const bool has_flat = f && f->total > 0;
+    if (has_flat) {
+        if (!unc_bf16 || !unc_residual || !flat_out_bf16) return fail(PSGD_ERR_VALUE, "null argument");
+        if (!f->bound) return fail(PSGD_ERR_STATE, "flat plan is not bound");
+        if (f->dtype != PSGD_F32 || f->device != p->device)
+            return fail(PSGD_ERR_VALUE, "psgd_aggregate_mixed_flat takes an fp32 flat plan (the uncompressed tensors' "
+                                        "residual) on the codec's device");
+    }
+    return mixed_impl(p, grads_bf16, residual, out_bf16, step, has_flat ? f : nullptr, unc_bf16, unc_residual,
+                      flat_out_bf16, static_cast<hipStream_t>(stream));
+}
+
+int psgd_aggregate_mixed(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,
+                         void* stream) {
+    return psgd_aggregate_mixed_flat(p, grads_bf16, residual, out_bf16, step, nullptr, nullptr, nullptr, nullptr,
+                                     stream);
+}
+
+}  // extern "C"

@@ -46,6 +46,7 @@ psgd_plan::~psgd_plan() {
         (void)hipEventDestroy(e.second);
     }
     ipc_release(this);
+    mixed_release(this);
     if (xerr_host) (void)hipHostFree(xerr_host);
     if (stamp_buf) (void)hipFree(stamp_buf);
 }
@@ -176,6 +177,7 @@ int psgd_plan_create(const int64_t* dims, const int32_t* ndims, int32_t num_tens
     p->fin_proj_on = env_int("PSGD_FIN_PROJ", 1) != 0;
     p->oe_on = env_int("PSGD_OE", 1) != 0;
     p->orth_chol = env_int("PSGD_ORTH_CHOL", 1) != 0;
+    p->mix_ingest_on = env_int("PSGD_MIXED_INGEST", 1) != 0;
 
     // output layout: dense, tensor order (what torch.cat / unflatten produce); a matrix
     // whose segment is not 16-byte aligned takes the scalar path

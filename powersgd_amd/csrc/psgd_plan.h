@@ -228,6 +228,7 @@ struct psgd_plan {
     // environment knobs, read once at create: PSGD_FUSE_FINAL, PSGD_FIN_PROJ, PSGD_OE (0: that
     // fused form is never used), PSGD_ORTH_CHOL (Cholesky-QR vs Householder)
     bool fuse_final_on = true, fin_proj_on = true, oe_on = true, orth_chol = true;
+    bool mix_ingest_on = true;   // PSGD_MIXED_INGEST (0: psgd_aggregate_mixed never takes the ingest fold; A/B runs)
     bool fin_ok = false;         // every matrix fits the fused final odd pass (K-term form)
     bool fin_proj = false;       // ... in its projection form (I = 2, psgd_aggregate only)
     int fin_smax = 0;
@@ -338,6 +339,23 @@ struct psgd_plan {
     bool xerr_set() const { return xerr_host && __atomic_load_n(xerr_host, __ATOMIC_ACQUIRE) != 0; }
     unsigned long long* stamp_buf = nullptr;  // diagnostic k_even stamps (PSGD_EVEN_STAMPS)
     size_t stamp_words = 0;
+    // psgd_aggregate_mixed (psgd_mixed.cpp): state of its own, created by the first mixed call or
+    // fold query of a bound plan; nothing of it lives in the caller's workspace (whose carve stays
+    // as it is), the device side is one small allocation owned by the plan
+    struct Mixed {
+        // admission of the mixed instances for the plan's current tiling (`key`): at least two
+        // waves per SIMD and no scratch, asked of the runtime like the fused final pass's
+        uint64_t key = ~uint64_t(0);
+        bool fin_in = false;       // single-pass k_final_odd_mix with the ingest fold
+        bool out[2] = {};          // the final pass of even / odd steps stores bf16
+        char* dev = nullptr;       // pointer tables of the bf16 gradients (TableCache slots)
+        size_t unc_cap = 0;        // ... and of the uncompressed bf16 gradients (entries)
+        char* unc_dev = nullptr;
+        TableCache src_tab, unc_tab;
+        psgd_runs* add = nullptr;  // the run-table ADD (k_runs_mix) of steps without an ingest fold
+        char* add_ws = nullptr;
+    };
+    Mixed* mixed = nullptr;
     int64_t xslot_off(int64_t step, int it) const {  // byte offset of a slot in every buffer
         return kXchgHeader + ((step & 1) * iters + it) * ipc_slot * int64_t(sizeof(float));
     }
@@ -444,6 +462,10 @@ struct StepCtx {
     // psgd_aggregate_ipc, ranks 2/4, two iterations: the exchange of iteration 0 left the summed
     // Q panels' Gram partials, so iteration 1 orthonormalises with k_orth_chain
     bool xgram = false;
+    // psgd_aggregate_mixed: the final pass (and the flat items riding in it) runs its mixed
+    // instance with these arguments; mix_in: the single-pass final kernel also ingests (ingest fold)
+    const MixArgs* mix = nullptr;
+    bool mix_in = false;
 };
 
 // psgd_step.cpp
@@ -455,5 +477,9 @@ int decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t step, i
 int flat_args(psgd_flat* f, void* const* tensors, void* flat, int32_t world, hipStream_t s, FlatArgs* out);
 // psgd_ipc.cpp: the plan's exchange region goes back to the process's arena
 void ipc_release(psgd_plan* p);
+// psgd_mixed.cpp: frees the plan's mixed state
+void mixed_release(psgd_plan* p);
+// psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
+int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
 
 }  // namespace psgd

@@ -416,7 +416,11 @@ int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t 
         std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
         if (int st = timing_begin(p, s, &ev, true)) return st;  // benchmark timing: the final pass
         TimedScope ts(ev);
-        PSGD_HIP(launch_final_odd(p->dtype, p->rbucket, fa.nres, fin_bucket(p->fin_smax), fa, nfin, s));
+        if (c.mix)  // psgd_aggregate_mixed: bf16 output, and the ingest fold of the single-pass form
+            PSGD_HIP(launch_final_mix(p->rbucket, fa.nres, fin_bucket(p->fin_smax), c.mix_in && it == 0, fa, *c.mix, nfin,
+                                      s, nullptr));
+        else
+            PSGD_HIP(launch_final_odd(p->dtype, p->rbucket, fa.nres, fin_bucket(p->fin_smax), fa, nfin, s));
         return PSGD_OK;
     }
 
@@ -496,6 +500,14 @@ int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t 
     return PSGD_OK;
 }
 
+int psgd::aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c) {
+    c.fuse = c.write_out = true;
+    for (int it = 0; it < p->iters; ++it)
+        if (int st = compress_impl(p, grads, step, it, s, c)) return st;
+    if (p->fused_final(step, true)) return PSGD_OK;  // output written by the fused last iteration
+    return decompress_impl(p, grads, c.out, step, 1, s, c);
+}
+
 int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s,
                           StepCtx c) {
     if (p->f64()) return decompress_f64(p, grads, out, step, world, s);
@@ -534,7 +546,10 @@ int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t s
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     if (int st = timing_begin(p, s, &ev, true)) return st;
     TimedScope ts(ev);
-    PSGD_HIP(launch_apply(p->dtype, p->rbucket, I, world == 1, aa, nt, s));
+    if (c.mix)  // psgd_aggregate_mixed (world size 1): bf16 output
+        PSGD_HIP(launch_apply_mix(p->rbucket, I, aa, *c.mix, nt, s, nullptr));
+    else
+        PSGD_HIP(launch_apply(p->dtype, p->rbucket, I, world == 1, aa, nt, s));
     return PSGD_OK;
 }
 
@@ -557,13 +572,9 @@ int bucket_span(const psgd_plan* p, int32_t b, psgd_plan::Span* sp) {
 // output written by the fused last iteration where the plan has one
 int aggregate_impl(psgd_plan* p, void* const* grads, void* out, int64_t step, hipStream_t s, const FlatArgs* fl) {
     StepCtx c;
-    c.fuse = c.write_out = true;
     c.fl = fl;
     c.out = out;
-    for (int it = 0; it < p->iters; ++it)
-        if (int st = compress_impl(p, grads, step, it, s, c)) return st;
-    if (p->fused_final(step, true)) return PSGD_OK;  // output written by the fused last iteration
-    return decompress_impl(p, grads, out, step, 1, s, c);
+    return aggregate_ctx(p, grads, step, s, c);
 }
 
 int check_terms(int32_t nterms, const float* const* a, const float* const* b) {

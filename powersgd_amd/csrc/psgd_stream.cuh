@@ -29,6 +29,8 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "psgd_internal.h"
 
 namespace psgd {
@@ -141,6 +143,34 @@ struct StIo<bf16_t> {
     template <int AUX = PSGD_ST_AUX>
     static __device__ __forceinline__ void st1(rsrc_t r, uint32_t off, float v) {
         __builtin_amdgcn_raw_buffer_store_b16(f2bf(v), r, off, 0, AUX);
+    }
+};
+// The bf16 output of an fp32 pass (the mixed instances of psgd_aggregate_mixed, MixArgs): the fp32
+// values are first pinned in exactly the form StIo<float> hands them to its store (one 128-bit
+// vector of their bits, or one dword), and only then rounded to bf16. The arithmetic that produces
+// them therefore reaches the same kind of sink as in the fp32 instance, and the compiler's choices
+// upstream (which products it contracts into fmas, what it packs) come out the same: the mixed
+// instances must round the very values the fp32 instances store (tests/
+// test_gpu_fp32_residual_fused.py compares them bit for bit). Rounding straight from the
+// expressions changed those choices (rank-1 sums of products, K-term and apply forms).
+struct bf16_pin_t {
+    uint16_t bits;
+};
+template <>
+struct StIo<bf16_pin_t> {
+    template <int AUX = PSGD_ST_AUX>
+    static __device__ __forceinline__ void st4(rsrc_t r, uint32_t off, const float (&v)[4]) {
+        typedef unsigned v4u __attribute__((ext_vector_type(4)));
+        v4u x = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+        asm volatile("" : "+v"(x));
+        const float w[4] = {__uint_as_float(x[0]), __uint_as_float(x[1]), __uint_as_float(x[2]), __uint_as_float(x[3])};
+        StIo<bf16_t>::template st4<AUX>(r, off, w);
+    }
+    template <int AUX = PSGD_ST_AUX>
+    static __device__ __forceinline__ void st1(rsrc_t r, uint32_t off, float v) {
+        uint32_t x = __float_as_uint(v);
+        asm volatile("" : "+v"(x));
+        StIo<bf16_t>::template st1<AUX>(r, off, __uint_as_float(x));
     }
 };
 // V consecutive elements at byte offset `off` of descriptor r
@@ -331,6 +361,46 @@ __device__ __forceinline__ void flat_pack_item(const FlatArgs& a, int item) {
             const uint32_t off = uint32_t(int64_t(q) * NT + threadIdx.x) * uint32_t(sizeof(T));
             StIo<T>::template st1<kStAuxSlot>(rf, off, a.world != 1 ? v[q] / w : v[q]);
             StIo<T>::st1(rx, off, 0.f);
+        }
+    }
+}
+
+// The flat item of psgd_aggregate_mixed (MixArgs): the uncompressed tensor's fp32 residual x and
+// its bf16 gradient g (2-byte aligned: element loads). flat (bf16) = f2bf(x + float(g)), one fp32
+// add, then x = +0.0 and g = +0.0: the run-table ADD, the flat pack and the run-table GATHER of
+// the three-stage flow on the item's elements, one read of each side and three writes.
+template <int NT>
+__device__ __forceinline__ void flat_mix_item(const FlatArgs& a, void* const* src, int item) {
+    constexpr int PER = kFlatItem / NT;
+    const FlatItem it = a.items[item];
+    const FlatEntry en = a.entries[it.entry];
+    const gptr<float> x = gmut<float>(a.tensors[en.tensor]);
+    const gptr<bf16_t> g = gmut<bf16_t>(src[en.tensor]);
+    const uint32_t cnt = uint32_t(en.numel - it.start < kFlatItem ? en.numel - it.start : kFlatItem);
+    const rsrc_t rx = make_rsrc(static_cast<float*>(a.tensors[en.tensor]) + it.start, cnt * 4u);
+    const rsrc_t rg = make_rsrc(static_cast<bf16_t*>(src[en.tensor]) + it.start, cnt * 2u);
+    const rsrc_t rf = make_rsrc(static_cast<bf16_t*>(a.flat) + en.off + it.start, cnt * 2u);
+    float v[PER], h[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int64_t j = it.start + int64_t(q) * NT + threadIdx.x;
+        const int64_t jc = j < en.numel ? j : 0;  // clamped, unconditional
+        v[q] = x[jc];
+        h[q] = bf2f(g[jc]);
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        keep(v[q]);
+        keep(h[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int64_t j = it.start + int64_t(q) * NT + threadIdx.x;
+        if (j < en.numel) {
+            const uint32_t e = uint32_t(int64_t(q) * NT + threadIdx.x);
+            StIo<bf16_t>::template st1<kStAuxSlot>(rf, e * 2u, v[q] + h[q]);
+            StIo<float>::st1(rx, e * 4u, 0.f);
+            StIo<bf16_t>::st1(rg, e * 2u, 0.f);
         }
     }
 }
@@ -1002,7 +1072,8 @@ hipError_t dispatch_odd_mfma(int R, int nres, const ProductArgs& a, int ntiles, 
 }
 
 // ------------------------------------------------------------------ apply ---------
-template <typename T, int R, int NI, bool SHARED, int V, bool ONT = false>
+// TO: the output's element type (the gradient's; bf16 over an fp32 residual in the mixed instances)
+template <typename T, int R, int NI, bool SHARED, int V, bool ONT = false, typename TO = T>
 __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t) {
     const TileGeom g = tile_geom<V>(d, t);
     const int r = d.r;
@@ -1010,10 +1081,10 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
     // residual and output destinations: this tile's rows through buffer descriptors (streaming
     // cache policy, 32-bit offsets from the tile's first row)
     T* const Dp = static_cast<T*>(a.rdst ? a.rdst[d.tensor] : a.grads[t.tensor]);
-    T* const Op = a.odst ? static_cast<T*>(a.odst[d.tensor]) : static_cast<T*>(a.out) + d.out_off;
+    TO* const Op = a.odst ? static_cast<TO*>(a.odst[d.tensor]) : static_cast<TO*>(a.out) + d.out_off;
     const uint32_t tb = uint32_t((g.row_end - g.row_begin) * g.m * int64_t(sizeof(T)));
     const rsrc_t rD = make_rsrc(Dp + g.row_begin * g.m, tb);
-    const rsrc_t rO = make_rsrc(Op + g.row_begin * g.m, tb);
+    const rsrc_t rO = make_rsrc(Op + g.row_begin * g.m, uint32_t((g.row_end - g.row_begin) * g.m * int64_t(sizeof(TO))));
     const int nt = NI > 0 ? NI : a.nterms;
     constexpr int NC = NI > 0 ? NI : 1;
     constexpr int NA = (NI > 0 && !SHARED) ? NI : 1;
@@ -1104,9 +1175,9 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
                 }
             }
             if (g.active && row + u * g.stride < g.row_end) {
-                const uint32_t off = uint32_t((b.rc[u] - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(T));
-                st_vec<T>(rD, off, b.x[u]);
-                st_vec<T, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, o);
+                const uint32_t eo = uint32_t((b.rc[u] - g.row_begin) * g.m + g.col0);
+                st_vec<T>(rD, eo * uint32_t(sizeof(T)), b.x[u]);
+                st_vec<TO, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
             }
         }
     };
@@ -1282,6 +1353,65 @@ __global__ __launch_bounds__(kBlock) void k_apply(ApplyArgs a) {
         }
     }
     apply_tile<T, R, NI, SHARED, 1, ONT>(a, d, t);
+}
+
+// The final pass of psgd_aggregate_mixed (MixArgs): k_apply's world-size-1 form (SHARED) on an
+// fp32 residual with the output stored as bf16, the flat items as flat_mix_item. Ranks 1 / 2 / 4.
+template <int R, int NI, bool ONT>
+__global__ __launch_bounds__(kBlock) void k_apply_mix(ApplyArgs a, MixArgs x) {
+    static_assert(R <= 4, "mixed instances: rank buckets 1, 2 and 4");
+    const int nf = a.flat.nitems;
+    if (int(blockIdx.x) < nf) {
+        flat_mix_item<kBlock>(a.flat, x.unc_src, blockIdx.x);
+        return;
+    }
+    const Tile t = a.tiles[blockIdx.x - nf];
+    const MatDesc d = a.mats[t.mat];
+    if (d.vec)
+        apply_tile<float, R, NI, true, 4, ONT, bf16_pin_t>(a, d, t);
+    else
+        apply_tile<float, R, NI, true, 1, ONT, bf16_pin_t>(a, d, t);
+}
+
+// resident waves per SIMD of a kernel at NT threads per workgroup; 0 when it uses scratch
+template <typename F>
+hipError_t resident_waves(F fn, int NT, int* waves) {
+    int blocks = 0;
+    hipFuncAttributes fa{};
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, NT, 0);
+    if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(fn));
+    if (e != hipSuccess) return e;
+    *waves = fa.localSizeBytes > 0 ? 0 : blocks * (NT / 64) / 4;
+    return hipSuccess;
+}
+
+template <int R>
+hipError_t dispatch_apply_mix_r(int nterms, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s,
+                                int* waves) {
+    const dim3 grid(ntiles + a.flat.nitems), block(kBlock);
+    const int NI = nterms <= 4 ? nterms : -1;  // register-cached factor terms, as dispatch_apply_r
+#define PSGD_AM(NN)                                                                                     \
+    do {                                                                                                \
+        if (waves) {                                                                                    \
+            const hipError_t e = a.out_nt ? resident_waves(&k_apply_mix<R, NN, true>, kBlock, waves)   \
+                                          : resident_waves(&k_apply_mix<R, NN, false>, kBlock, waves); \
+            if (e != hipSuccess) return e;                                                              \
+        }                                                                                               \
+        if (ntiles + a.flat.nitems == 0) return hipSuccess;                                             \
+        if (a.out_nt)                                                                                   \
+            timed_launch(&k_apply_mix<R, NN, true>, grid, block, s, a, x);                              \
+        else                                                                                            \
+            timed_launch(&k_apply_mix<R, NN, false>, grid, block, s, a, x);                             \
+    } while (0)
+    switch (NI) {
+        case 1: PSGD_AM(1); break;
+        case 2: PSGD_AM(2); break;
+        case 3: PSGD_AM(3); break;
+        case 4: PSGD_AM(4); break;
+        default: PSGD_AM(-1); break;
+    }
+#undef PSGD_AM
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ dispatch ------

@@ -15,6 +15,13 @@ gradients are *consumed*:
 so ``optimizer_step`` works unchanged: it restores ``p.grad`` to the (zeroed) gradients and the
 next backward accumulates fresh gradients only. Cost against ``PowerSGD`` on the same bf16
 gradients: the two element-wise passes, an fp32 codec step, 4 bytes of state per parameter.
+
+``fused=True`` runs the same step as ONE library call (psgd_aggregate_mixed, include/psgd.h)
+wherever it applies (one process, a compressing step, rank bucket 1 / 2 / 4): the codec's final
+pass stores the bf16 averages itself (no GATHER pass), and where a step is one gradient pass
+(one iteration per step, odd steps) that pass also ingests the bf16 gradients (no ADD pass; on the
+other steps the library launches the ADD). Bit for bit the three-stage flow above; every other
+case runs it.
 """
 from __future__ import annotations
 
@@ -25,16 +32,19 @@ import torch
 
 from . import _lib
 from .powersgd import Aggregator, Config, PowerSGD, _output_slab, _psgd_host, _require_device, _stream, _views
+from .utils import is_distributed
 
 
 class Fp32ResidualPowerSGD(Aggregator):
     """``PowerSGD(params, config)`` for bfloat16 ``params`` on one GPU per process, with an fp32
     residual owned by the aggregator: ``residual`` (flat), ``views`` (per parameter), ``inner``
-    (the fp32 ``PowerSGD`` over ``views``)."""
+    (the fp32 ``PowerSGD`` over ``views``). ``fused``: take the one-call fused step where it
+    applies (module docstring); same results, bit for bit."""
 
-    def __init__(self, params: List[torch.Tensor], config: Config):
+    def __init__(self, params: List[torch.Tensor], config: Config, fused: bool = False):
         params = list(params)
         self.config = config
+        self.fused = bool(fused)
         self.device = params[0].device  # IndexError on an empty list, as PowerSGD
         bad = [p.dtype for p in params if p.dtype != torch.bfloat16]
         if bad:
@@ -63,6 +73,7 @@ class Fp32ResidualPowerSGD(Aggregator):
             r.bind(self._dev_index, ws.data_ptr())
             self._ws.append(ws)
         self._slab = _output_slab(shapes, _lib.PSGD_BF16, self._dev_index)
+        self._fused_state = None  # built by the first fused step
 
     @property
     def step_counter(self) -> int:
@@ -79,12 +90,65 @@ class Fp32ResidualPowerSGD(Aggregator):
             gradients = list(gradients)
         self._table.fill(gradients)  # count / dtype / device / shape / contiguity, as PowerSGD
         stream = _stream(self.device)
+        if self.fused and self._fused_applies():
+            return self._aggregate_fused(gradients, stream)
         self._add.add_list(self._table.comp_addr(), ctypes.addressof(self._res_ptrs), True, stream)
         avg = self.inner.aggregate(self.views)  # fp32; leaves the new residual in self.views
         _psgd_host.fill_list(avg, ctypes.addressof(self._out_ptrs), _lib.PSGD_F32, self._dev_index)
         outs = self._slab.get()
         self._gather.gather(self._slab.data_ptr(), ctypes.addressof(self._out_ptrs), stream)
         return outs
+
+    def _fused_applies(self) -> bool:
+        """The step about to run compresses, in one process, on a plan psgd_aggregate_mixed serves
+        (both step parities: a plan is eligible or not as a whole)."""
+        inner = self.inner
+        if is_distributed() or inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
+            return False
+        plan = inner._powersgd._plan
+        return plan.mixed_folds(0)[1] == 1 and plan.mixed_folds(1)[1] == 1
+
+    def fused_folds(self):
+        """``(fold_in, fold_out)`` of the NEXT ``aggregate`` call: 1 where the ingest of the bf16
+        gradients / the bf16 rounding of the averages will run inside the codec's own gradient
+        pass (psgd_plan_mixed_folds); ``(0, 0)`` whenever that call runs the three-stage flow
+        (``fused=False``, a warm-up step, more than one process, a plan the fused call refuses)."""
+        if not (self.fused and self._fused_applies()):
+            return (0, 0)
+        return self.inner._powersgd._plan.mixed_folds(self.inner._powersgd.step_counter)
+
+    def _aggregate_fused(self, gradients: List[torch.Tensor], stream: int) -> List[torch.Tensor]:
+        """``PowerSGD.aggregate`` of ``inner`` on the residual, as psgd_aggregate_mixed[_flat]: the
+        same bookkeeping (step counters, split by the compression mask, merge order), the bf16
+        gradients consumed and the bf16 averages written inside the library call."""
+        inner, codec = self.inner, self.inner._powersgd
+        st = self._fused_state
+        if st is None:
+            mask = inner.is_compressed_mask
+            shapes = [v.shape for v in self.views]
+            st = self._fused_state = {
+                # the bf16 gradients and the fp32 residual views, split like PowerSGD._split
+                "grads": _psgd_host.PtrTable([list(s) for s in shapes], mask, _lib.PSGD_BF16, self._dev_index),
+                "comp_slab": _output_slab([s for s, c in zip(shapes, mask) if c], _lib.PSGD_BF16, self._dev_index),
+                "unc_slab": (_output_slab([s for s, c in zip(shapes, mask) if not c], _lib.PSGD_BF16, self._dev_index)
+                             if inner._unc is not None else None),
+            }
+        st["grads"].fill(gradients)
+        inner._table.fill(self.views)
+        inner.step_counter += 1
+        outs = st["comp_slab"].get()
+        if inner._unc is not None:
+            unc = st["unc_slab"].get()
+            codec._plan.aggregate_mixed(st["grads"].comp_addr(), inner._table.comp_addr(), st["comp_slab"].data_ptr(),
+                                        codec.step_counter, stream, flat=inner._unc.plan,
+                                        unc_bf16=st["grads"].unc_addr(), unc_residual=inner._table.unc_addr(),
+                                        flat_out=st["unc_slab"].data_ptr())
+            outs = outs + unc
+        else:
+            codec._plan.aggregate_mixed(st["grads"].comp_addr(), inner._table.comp_addr(), st["comp_slab"].data_ptr(),
+                                        codec.step_counter, stream)
+        codec.step_counter += 1
+        return [outs[i] for i in inner._order]
 
     def close(self) -> None:
         """Collective: release the codec's multi-GPU transports (PowerSGD.close)."""

@@ -400,6 +400,48 @@ int psgd_aggregate_mixed_flat(psgd_plan* plan, void* const* grads_bf16, void* co
                               void* const* unc_residual, void* flat_out_bf16, void* stream);
 int psgd_plan_mixed_folds(const psgd_plan* plan, int64_t step, int32_t* fold_in, int32_t* fold_out);
 
+/* ------------------- ... at world size W over a communicator, in one call ---------------------- */
+/* The mixed form of psgd_aggregate_comm. DEFINED as this sequence, and equal to it bit for bit,
+ * with nothing else observable:
+ *   1. residual[i][j] += float(grads_bf16[i][j]), grads_bf16[i][j] = +0.0; the uncompressed
+ *      tensors likewise: unc_residual += float(unc_bf16), unc_bf16 = +0.0
+ *   2. psgd_aggregate_comm(plan, residual, avg_f32, step, flat, unc_residual, flat_f32, comm): the
+ *      same kernels, the same collectives in the same order and the same count (num_iters_per_step
+ *      all-reduces; the flat tail holds x / W and is grouped with the last factor's)
+ *   3. out_bf16 = bf16(avg_f32), flat_out_bf16 = bf16(flat_f32)   round to nearest even
+ * Where the stages run:
+ *   output fold  every step: the final pass of the W > 1 sequence stores its output as bf16, the
+ *                residual stays fp32. That pass is k_apply with two term sets (the residual from
+ *                the local factors, the output alpha x the all-reduced ones), or, on steps whose
+ *                last iteration is odd on a plan with the K-term fused final pass (rank buckets 1
+ *                and 2), the output pass k_lowrank_out that follows k_final_odd. With a 1-rank
+ *                communicator the two-term-set pass is the world-size-1 instance of
+ *                psgd_aggregate_mixed.
+ *   ingest       never folded (fold_in is 0): the library launches the run-table ADD first. The
+ *                W > 1 sequence has no single-pass kernel to fold it into.
+ *   flat tail    the all-reduce sums fp32 values, so the tail is staged in an fp32 buffer of
+ *                flat->total floats owned by the plan (made or grown by the first call that needs
+ *                it): stage = (x + float(g)) / W, x = g = +0.0 in a launch of its own before the
+ *                first collective; flat_out_bf16 = bf16(stage) in the leading workgroups of the
+ *                final launch (a launch of its own after the world-size-1 instance).
+ * Arguments as psgd_aggregate_mixed_flat (flat null or empty: no uncompressed tensors) and
+ * psgd_aggregate_comm. Eligible: a bound PSGD_F32 plan, rank bucket 1, 2 or 4, not wide, one
+ * bucket, whose final-pass instance of BOTH step parities is admitted (at least two waves per SIMD,
+ * no scratch; asked of the runtime) for the communicator's world size. Anything else:
+ * PSGD_ERR_VALUE before anything is launched or any collective issued, the communicator stays
+ * usable, and psgd_plan_mixed_folds_comm reports 0 / 0. A poisoned communicator is refused at
+ * entry (PSGD_ERR_STATE); any other failure past the argument checks poisons it, as in
+ * psgd_aggregate_comm.
+ * psgd_plan_mixed_folds_comm: the folds of `step` at world size `world` (>= 1): fold_in always 0,
+ * fold_out 1 for an eligible plan. On an unbound plan the answer is this build's on the current
+ * device (0 / 0 without one). */
+int psgd_aggregate_mixed_comm(psgd_plan* plan, void* const* grads_bf16, void* const* residual,
+                              void* out_bf16, int64_t step, psgd_flat* flat, void* const* unc_bf16,
+                              void* const* unc_residual, void* flat_out_bf16, psgd_comm* comm,
+                              void* stream);
+int psgd_plan_mixed_folds_comm(const psgd_plan* plan, int64_t step, int32_t world,
+                               int32_t* fold_in, int32_t* fold_out);
+
 #ifdef __cplusplus
 }
 #endif

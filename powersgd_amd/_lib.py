@@ -80,6 +80,8 @@ _SIGNATURES = {
     "psgd_aggregate_mixed": ([_vp, _vp, _vp, _vp, _i64, _vp], _i32),
     "psgd_aggregate_mixed_flat": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_plan_mixed_folds": ([_vp, _i64, _P_i32, _P_i32], _i32),
+    "psgd_aggregate_mixed_comm": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_mixed_folds_comm": ([_vp, _i64, _i32, _P_i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -234,6 +236,23 @@ class Plan:
         else:
             check(lib().psgd_aggregate_mixed_flat(self._h, grads_bf16, residual, out_ptr, step, flat._h, unc_bf16,
                                                   unc_residual, flat_out, stream))
+
+    # --- ... at world size W over the library's communicator
+    def mixed_folds_comm(self, step: int, world: int):
+        """(fold_in, fold_out) of ``step`` under ``aggregate_mixed_comm`` at world size ``world``
+        (psgd_plan_mixed_folds_comm): fold_in is always 0 (the ADD is a launch of its own), fold_out 1
+        where the final pass stores the bf16 averages itself; (0, 0) for a plan the call refuses."""
+        fi, fo = _i32(), _i32()
+        check(lib().psgd_plan_mixed_folds_comm(self._h, step, world, ctypes.byref(fi), ctypes.byref(fo)))
+        return int(fi.value), int(fo.value)
+
+    def aggregate_mixed_comm(self, grads_bf16, residual, out_ptr: int, step: int, comm: "Comm", stream: int,
+                             flat=None, unc_bf16=None, unc_residual=None, flat_out: int = 0) -> None:
+        """psgd_aggregate_mixed_comm. Raises ``ValueError`` for a plan it does not serve, before
+        anything is launched or any collective issued."""
+        check(lib().psgd_aggregate_mixed_comm(self._h, grads_bf16, residual, out_ptr, step,
+                                              flat._h if flat is not None else None, unc_bf16, unc_residual,
+                                              flat_out or None, comm._h if comm is not None else None, stream))
 
     # --- buckets of shape groups (W > 1 comm/compute overlap)
     def set_buckets(self, group_end: Sequence[int]) -> None:

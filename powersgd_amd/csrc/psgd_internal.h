@@ -463,9 +463,17 @@ hipError_t launch_runs_mix(int bucket_dtype, int tensor_dtype, int mode, const R
 //                 residual. (The same fold in k_even was built and measured slower than the
 //                 run-table ADD it replaces, DESIGN.md section 10: not kept.)
 //   flat items    an uncompressed tensor's item does both: flat = bf16(x + float(src)), x = src = +0.0
+// psgd_aggregate_mixed_comm (world size W over a communicator) keeps the output fold only: the
+// final pass of the W > 1 sequence (k_apply with two term sets, or k_lowrank_out after a fused
+// k_final_odd) stores bf16. The all-reduce sums fp32 values, so the uncompressed tensors travel
+// through `stage` (fp32, the flat plan's layout, owned by the plan):
+//   ingest-pack   stage = (x + float(src)) / W, x = src = +0.0   a launch of its own, before the
+//                 first collective (flat_ingest_item)
+//   round         flat = bf16(stage)   leading workgroups of the final launch (flat_round_item)
 struct MixArgs {
     void* const* src;      // bf16 gradients of the plan's tensors (gradient-table order), ingest fold
     void* const* unc_src;  // bf16 gradients of the uncompressed tensors (the flat plan's order)
+    float* stage;          // psgd_aggregate_mixed_comm: fp32 staging of the flat tail, else null
 };
 // psgd_mixed_{final,apply}.hip. ntiles == 0: no launch; `*waves` (if non-null) receives
 // the resident waves per SIMD of the instance that would run, 0 when it uses scratch.
@@ -473,6 +481,17 @@ hipError_t launch_final_mix(int R, int nres, int smax, bool ingest, const FinalA
                             hipStream_t s, int* waves);
 hipError_t launch_apply_mix(int R, int nterms, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s,
                             int* waves);
+// psgd_mixed_comm.hip: the final pass of psgd_aggregate_mixed_comm at W > 1 (`waves` as above).
+// launch_apply_mix_w: k_apply's two-term-set form with the output stored as bf16;
+// launch_lowrank_mix: k_lowrank_out's (the output pass after a fused k_final_odd), rank buckets 1 / 2.
+// In both, a.flat's items are round items (flat_round_item) and come first. launch_flat_ingest /
+// launch_flat_round: the flat items as launches of their own.
+hipError_t launch_apply_mix_w(int R, int nterms, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s,
+                              int* waves);
+hipError_t launch_lowrank_mix(int R, int nterms, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s,
+                              int* waves);
+hipError_t launch_flat_ingest(const FlatArgs& a, const MixArgs& x, hipStream_t s);
+hipError_t launch_flat_round(const FlatArgs& a, const MixArgs& x, hipStream_t s);
 
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),

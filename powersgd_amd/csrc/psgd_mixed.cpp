@@ -13,7 +13,12 @@
 //                run-table ADD as a launch of its own first (first pass k_even: the fold was built
 //                and measured slower than the ADD it replaces; k_final_oe
 //                and the unfused odd product: no fold built)
+// psgd_aggregate_mixed_comm / psgd_plan_mixed_folds_comm: the same at world size W over a
+// communicator, defined as the ADD, psgd_aggregate_comm on the residual and the GATHER. The output
+// fold alone, on every step (admission per communicator kind, admit_comm); the ADD is always a
+// launch of its own, first; the flat tail is staged in fp32 (Mixed::stage) around its collective.
 #include <memory>
+#include <string>
 
 #include "psgd_plan.h"
 
@@ -57,6 +62,39 @@ void admit(psgd_plan* p) {
     }
 }
 
+// psgd_aggregate_mixed_comm: the bf16-output instance of the step's final pass as
+// aggregate_comm_ctx / decompress_impl pick it: after a fused k_final_odd (fin_ok, the last
+// iteration odd) the output pass k_lowrank_mix; else k_apply_mix_w (two term sets, W > 1) or, with
+// a 1-rank communicator, the world-size-1 k_apply_mix
+void admit_comm(psgd_plan* p) {
+    psgd_plan::Mixed& m = *p->mixed;
+    const uint64_t key = uint64_t(p->fin_ok) | uint64_t(uint32_t(p->out_nt)) << 8;
+    if (m.comm_key == key) return;
+    m.comm_key = key;
+    const MixArgs none{};
+    for (int one = 0; one < 2; ++one)
+        for (int par = 0; par < 2; ++par) {
+            int w = 0;
+            ApplyArgs aa{};
+            hipError_t e;
+            if (p->fused_final(par, false)) {
+                e = launch_lowrank_mix(p->rbucket, p->iters, aa, none, 0, nullptr, &w);
+            } else if (one) {
+                aa.out_nt = p->out_nt;
+                e = launch_apply_mix(p->rbucket, p->iters, aa, none, 0, nullptr, &w);
+            } else {
+                e = launch_apply_mix_w(p->rbucket, p->iters, aa, none, 0, nullptr, &w);
+            }
+            m.comm_out[one][par] = admitted(e, w);
+        }
+}
+
+bool comm_eligible(const psgd_plan* p, int world) {
+    const psgd_plan::Mixed& m = *p->mixed;
+    const int one = world == 1 ? 1 : 0;
+    return m.comm_out[one][0] && m.comm_out[one][1];
+}
+
 // The plan's mixed state: the bf16 gradients' pointer tables and the run-table ADD, device side in
 // one allocation of the plan's own (made once, by the first call on a bound plan)
 int ensure(psgd_plan* p) {
@@ -91,6 +129,26 @@ void folds_at(const psgd_plan* p, int64_t step, int32_t* in, int32_t* out) {
     *in = eligible && single && m.fin_in ? 1 : 0;
 }
 
+// room for the uncompressed bf16 gradients' pointer table (first call, or a larger flat plan than
+// the last one's), and the null checks of both tensor lists
+int unc_table(psgd_plan::Mixed& m, psgd_flat* f, void* const* unc, void* const* unc_residual, hipStream_t s) {
+    if (size_t(f->count) > m.unc_cap) {
+        PSGD_HIP(hipStreamSynchronize(s));
+        m.unc_tab.release();
+        if (m.unc_dev) PSGD_HIP(hipFree(m.unc_dev));
+        m.unc_dev = nullptr;
+        PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&m.unc_dev), TableCache::bytes(size_t(f->count))));
+        m.unc_cap = size_t(f->count);
+        m.unc_tab.bind(m.unc_dev, size_t(f->count));
+    } else if (m.unc_tab.n != size_t(f->count)) {
+        PSGD_HIP(hipStreamSynchronize(s));
+        m.unc_tab.bind(m.unc_dev, size_t(f->count));
+    }
+    for (int32_t i = 0; i < f->count; ++i)
+        if (!unc[i] || !unc_residual[i]) return fail(PSGD_ERR_VALUE, "null uncompressed tensor pointer");
+    return PSGD_OK;
+}
+
 int mixed_impl(psgd_plan* p, void* const* grads, void* const* residual, void* out, int64_t step, psgd_flat* f,
                void* const* unc, void* const* unc_residual, void* flat_out, hipStream_t s) {
     if (const char* why = ineligible(p)) return fail(PSGD_ERR_VALUE, why);
@@ -114,20 +172,7 @@ int mixed_impl(psgd_plan* p, void* const* grads, void* const* residual, void* ou
     FlatArgs fa{};
     MixArgs x{};
     if (f) {
-        if (size_t(f->count) > m.unc_cap) {  // (first call, or a larger flat plan than the last one's)
-            PSGD_HIP(hipStreamSynchronize(s));
-            m.unc_tab.release();
-            if (m.unc_dev) PSGD_HIP(hipFree(m.unc_dev));
-            m.unc_dev = nullptr;
-            PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&m.unc_dev), TableCache::bytes(size_t(f->count))));
-            m.unc_cap = size_t(f->count);
-            m.unc_tab.bind(m.unc_dev, size_t(f->count));
-        } else if (m.unc_tab.n != size_t(f->count)) {
-            PSGD_HIP(hipStreamSynchronize(s));
-            m.unc_tab.bind(m.unc_dev, size_t(f->count));
-        }
-        for (int32_t i = 0; i < f->count; ++i)
-            if (!unc[i] || !unc_residual[i]) return fail(PSGD_ERR_VALUE, "null uncompressed tensor pointer");
+        if (int st = unc_table(m, f, unc, unc_residual, s)) return st;
         if (int st = flat_args(f, unc_residual, flat_out, 1, s, &fa)) return st;
         PSGD_HIP(m.unc_tab.select(unc, s));
         x.unc_src = m.unc_tab.table();
@@ -146,6 +191,41 @@ int mixed_impl(psgd_plan* p, void* const* grads, void* const* residual, void* ou
     return aggregate_ctx(p, residual, step, s, c);
 }
 
+// psgd_aggregate_mixed_comm past its argument checks. *refused: the plan has no admitted instance
+// (nothing launched, no collective issued: the communicator stays usable)
+int mixed_comm_impl(psgd_plan* p, void* const* grads, void* const* residual, void* out, int64_t step, psgd_flat* f,
+                    void* const* unc, void* const* unc_residual, void* flat_out, psgd_comm* comm, hipStream_t s,
+                    bool* refused) {
+    DevScope scope(p->device);
+    if (int st = ensure(p)) return st;
+    psgd_plan::Mixed& m = *p->mixed;
+    // the tiling the step will run on (the residual's alignment decides the vector layout)
+    if (int st = refresh_pointers(p, residual, s)) return st;
+    admit_comm(p);
+    if (!comm_eligible(p, comm_world(comm))) {
+        *refused = true;
+        return fail(PSGD_ERR_VALUE, "psgd_aggregate_mixed_comm: no admitted bf16-output instance of this plan's final "
+                                    "pass (two waves per SIMD, no scratch)");
+    }
+    MixArgs x{};
+    if (f) {
+        if (int st = unc_table(m, f, unc, unc_residual, s)) return st;
+        if (size_t(f->total) > m.stage_cap) {  // (first call, or a larger flat plan than the last one's)
+            PSGD_HIP(hipStreamSynchronize(s));
+            if (m.stage) PSGD_HIP(hipFree(m.stage));
+            m.stage = nullptr;
+            m.stage_cap = 0;
+            PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&m.stage), size_t(f->total) * sizeof(float)));
+            m.stage_cap = size_t(f->total);
+        }
+        PSGD_HIP(m.unc_tab.select(unc, s));
+        x.unc_src = m.unc_tab.table();
+        x.stage = m.stage;
+    }
+    if (int st = psgd_runs_add_list(m.add, grads, residual, 1, s)) return st;
+    return aggregate_comm_ctx(p, residual, out, step, f, unc_residual, flat_out, comm, s, &x);
+}
+
 }  // namespace
 
 void psgd::mixed_release(psgd_plan* p) {
@@ -156,6 +236,7 @@ void psgd::mixed_release(psgd_plan* p) {
     if (m->add) (void)psgd_runs_destroy(m->add);
     if (m->dev) (void)hipFree(m->dev);
     if (m->unc_dev) (void)hipFree(m->unc_dev);
+    if (m->stage) (void)hipFree(m->stage);
     delete m;
     p->mixed = nullptr;
 }
@@ -204,6 +285,66 @@ int psgd_aggregate_mixed_flat(psgd_plan* p, void* const* grads_bf16, void* const
     }
     return mixed_impl(p, grads_bf16, residual, out_bf16, step, has_flat ? f : nullptr, unc_bf16, unc_residual,
                       flat_out_bf16, static_cast<hipStream_t>(stream));
+}
+
+int psgd_plan_mixed_folds_comm(const psgd_plan* plan, int64_t step, int32_t world, int32_t* fold_in,
+                               int32_t* fold_out) {
+    if (!plan || !fold_in || !fold_out) return fail(PSGD_ERR_VALUE, "null argument");
+    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
+    if (world < 1) return fail(PSGD_ERR_VALUE, "world size must be >= 1");
+    *fold_in = *fold_out = 0;  // no ingest fold in this form: the ADD is always a launch of its own
+    if (ineligible(plan)) return PSGD_OK;
+    psgd_plan* p = const_cast<psgd_plan*>(plan);
+    DevScope scope(p->device);
+    if (!p->mixed) {
+        if (!p->bound) {  // no device yet: ask without keeping device state
+            psgd_plan::Mixed tmp;
+            p->mixed = &tmp;
+            admit_comm(p);
+            *fold_out = comm_eligible(p, world) ? 1 : 0;
+            p->mixed = nullptr;
+            return PSGD_OK;
+        }
+        if (int st = ensure(p)) return st;
+    }
+    admit_comm(p);
+    *fold_out = comm_eligible(p, world) ? 1 : 0;
+    return PSGD_OK;
+}
+
+int psgd_aggregate_mixed_comm(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16,
+                              int64_t step, psgd_flat* f, void* const* unc_bf16, void* const* unc_residual,
+                              void* flat_out_bf16, psgd_comm* comm, void* stream) {
+    if (!p || !grads_bf16 || !residual || !out_bf16 || !comm) return fail(PSGD_ERR_VALUE, "null argument");
+    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
+    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
+    if (reinterpret_cast<uintptr_t>(out_bf16) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    const bool has_flat = f && f->total > 0;
+    if (has_flat) {
+        if (!unc_bf16 || !unc_residual || !flat_out_bf16) return fail(PSGD_ERR_VALUE, "null argument");
+        if (!f->bound) return fail(PSGD_ERR_STATE, "flat plan is not bound");
+        if (f->dtype != PSGD_F32 || f->device != p->device)
+            return fail(PSGD_ERR_VALUE, "psgd_aggregate_mixed_comm takes an fp32 flat plan (the uncompressed tensors' "
+                                        "residual) on the codec's device");
+    }
+    if (const char* why = ineligible(p)) return fail(PSGD_ERR_VALUE, why);
+    for (size_t i = 0; i < p->shapes.size(); ++i) {
+        if (!grads_bf16[i] || !residual[i]) return fail(PSGD_ERR_VALUE, "null gradient pointer");
+        if (reinterpret_cast<uintptr_t>(grads_bf16[i]) % 2) return fail(PSGD_ERR_LAYOUT, "bf16 gradients must be 2-byte aligned");
+        if (reinterpret_cast<uintptr_t>(residual[i]) % 4) return fail(PSGD_ERR_LAYOUT, "the fp32 residual must be 4-byte aligned");
+    }
+    // a poisoned communicator is refused before the step launches anything: the caller's
+    // gradients, the residual and the P/Q state stay as they were
+    std::string why;
+    if (comm_poisoned(comm, &why))
+        return fail(PSGD_ERR_STATE, ("communicator unusable after an earlier failure: " + why).c_str());
+    bool refused = false;
+    const int st = mixed_comm_impl(p, grads_bf16, residual, out_bf16, step, has_flat ? f : nullptr, unc_bf16,
+                                   unc_residual, flat_out_bf16, comm, static_cast<hipStream_t>(stream), &refused);
+    // a failure past the argument checks can leave this rank's collective sequence short of its
+    // peers': the communicator refuses every later call (psgd_comm.cpp, comm_poison)
+    if (st && !refused) comm_poison(comm, psgd_last_error());
+    return st;
 }
 
 int psgd_aggregate_mixed(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,

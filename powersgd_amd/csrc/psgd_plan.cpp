@@ -53,7 +53,7 @@ psgd_plan::~psgd_plan() {
 
 extern "C" {
 
-int psgd_version(void) { return 101; }
+int psgd_version(void) { return 102; }
 
 const char* psgd_last_error(void) { return g_err.c_str(); }
 

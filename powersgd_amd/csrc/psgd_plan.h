@@ -354,6 +354,14 @@ struct psgd_plan {
         TableCache src_tab, unc_tab;
         psgd_runs* add = nullptr;  // the run-table ADD (k_runs_mix) of steps without an ingest fold
         char* add_ws = nullptr;
+        // psgd_aggregate_mixed_comm: admission of the final pass's bf16-output instance per
+        // communicator kind ([0]: world size > 1, [1]: a 1-rank communicator) and step parity, and
+        // the fp32 staging of the flat tail around its collective (made or grown by the first
+        // call that needs it, like unc_dev)
+        uint64_t comm_key = ~uint64_t(0);
+        bool comm_out[2][2] = {};
+        float* stage = nullptr;
+        size_t stage_cap = 0;      // floats
     };
     Mixed* mixed = nullptr;
     int64_t xslot_off(int64_t step, int it) const {  // byte offset of a slot in every buffer
@@ -481,5 +489,8 @@ void ipc_release(psgd_plan* p);
 void mixed_release(psgd_plan* p);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
 int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
+// psgd_step.cpp: the world-size-W step of psgd_aggregate_comm; with `mix`, of psgd_aggregate_mixed_comm
+int aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
+                       void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix);
 
 }  // namespace psgd

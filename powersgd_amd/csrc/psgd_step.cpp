@@ -537,6 +537,11 @@ int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t s
     if (p->fused_final(step, false)) {
         // the residual was written by the fused last iteration: output only
         aa.ntiles = nt;
+        if (c.mix) {  // psgd_aggregate_mixed_comm: bf16 output, the flat tail's round items first
+            if (c.fl) aa.flat = *c.fl;
+            if (nt + aa.flat.nitems > 0) PSGD_HIP(launch_lowrank_mix(p->rbucket, I, aa, *c.mix, nt, s, nullptr));
+            return PSGD_OK;
+        }
         if (nt > 0) PSGD_HIP(launch_lowrank_out(p->dtype, p->rbucket, I, aa, nt, s));
         return PSGD_OK;
     }
@@ -546,8 +551,10 @@ int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t s
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     if (int st = timing_begin(p, s, &ev, true)) return st;
     TimedScope ts(ev);
-    if (c.mix)  // psgd_aggregate_mixed (world size 1): bf16 output
+    if (c.mix && world == 1)  // psgd_aggregate_mixed (world size 1): bf16 output
         PSGD_HIP(launch_apply_mix(p->rbucket, I, aa, *c.mix, nt, s, nullptr));
+    else if (c.mix)  // psgd_aggregate_mixed_comm at W > 1: two term sets, bf16 output
+        PSGD_HIP(launch_apply_mix_w(p->rbucket, I, aa, *c.mix, nt, s, nullptr));
     else
         PSGD_HIP(launch_apply(p->dtype, p->rbucket, I, world == 1, aa, nt, s));
     return PSGD_OK;
@@ -597,19 +604,26 @@ int refresh_table(psgd_plan* p, void* const* ptrs, TableCache& tab, hipStream_t 
     return PSGD_OK;
 }
 
-int aggregate_comm_body(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f,
-                        void* const* unc, void* flat_out, psgd_comm* comm, hipStream_t s) {
+}  // namespace
+
+// `mix` (psgd_aggregate_mixed_comm): `grads` the fp32 residual, `out` / `flat_out` bf16, `unc` the
+// uncompressed tensors' fp32 residual; the flat tail is staged in mix->stage (fp32) around its
+// collective: ingest-pack in a launch of its own first, the round items in the final launch
+int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f,
+                             void* const* unc, void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix) {
     const bool has_flat = f != nullptr;
     const int world = comm_world(comm);
     // x / W into the flat buffer, x = 0 (utils.py:43-47, powersgd.py:29-30): inside the first
     // even product's launch when the step starts even, else its own launch
     FlatArgs fa{};
-    const bool fold = has_flat && p->even(step, 0) && !p->wide();  // wide products carry no flat pack
-    if (fold) {
+    const bool fold = has_flat && !mix && p->even(step, 0) && !p->wide();  // wide products carry no flat pack
+    if (fold || (mix && has_flat)) {
         if (int st = flat_args(f, unc, flat_out, world, s, &fa)) return st;
+        if (mix) PSGD_HIP(launch_flat_ingest(fa, *mix, s));
     } else if (has_flat) {
         if (int st = psgd_flat_pack(f, unc, flat_out, world, s)) return st;
     }
+    float* const tail = mix ? mix->stage : static_cast<float*>(flat_out);
     StepCtx c;
     c.fl = fold ? &fa : nullptr;
     for (int it = 0; it < p->iters; ++it) {
@@ -617,11 +631,26 @@ int aggregate_comm_body(psgd_plan* p, void* const* grads, void* out, int64_t ste
         const bool e = p->even(step, it);
         const bool last = it == p->iters - 1;
         if (int st = comm_allreduce(comm, e ? p->Q : p->P, size_t(e ? p->qtot : p->ptot),
-                                    last && has_flat ? static_cast<float*>(flat_out) : nullptr,
-                                    last && has_flat ? size_t(f->total) : 0, s))
+                                    last && has_flat ? tail : nullptr, last && has_flat ? size_t(f->total) : 0, s))
             return st;
     }
-    return decompress_impl(p, grads, out, step, world, s, StepCtx{});
+    if (!mix) return decompress_impl(p, grads, out, step, world, s, StepCtx{});
+    // the round items ride in every final launch built for them; a 1-rank communicator's unfused
+    // final pass is the world-size-1 instance, whose flat items ingest: the round follows it
+    const bool ride = world > 1 || p->fused_final(step, false);
+    StepCtx d;
+    d.mix = mix;
+    d.fl = has_flat && ride ? &fa : nullptr;
+    if (int st = decompress_impl(p, grads, out, step, world, s, d)) return st;
+    if (has_flat && !ride) PSGD_HIP(launch_flat_round(fa, *mix, s));
+    return PSGD_OK;
+}
+
+namespace {
+
+int aggregate_comm_body(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f,
+                        void* const* unc, void* flat_out, psgd_comm* comm, hipStream_t s) {
+    return aggregate_comm_ctx(p, grads, out, step, f, unc, flat_out, comm, s, nullptr);
 }
 
 }  // namespace

@@ -405,6 +405,75 @@ __device__ __forceinline__ void flat_mix_item(const FlatArgs& a, void* const* sr
     }
 }
 
+// The flat items of psgd_aggregate_mixed_comm (world size W: the flat tail is all-reduced in fp32,
+// so it is staged in `stage`, fp32 in the flat plan's layout, and rounded after the collective).
+// Ingest-pack: stage = (x + float(g)) / W (ONE fp32 add, then flat_pack_item's division; an exact
+// copy of the sum at W = 1), then x = +0.0 and g = +0.0: the run-table ADD and the flat pack of
+// the three-stage flow on the item's elements.
+template <int NT>
+__device__ __forceinline__ void flat_ingest_item(const FlatArgs& a, void* const* src, float* stage, int item) {
+    constexpr int PER = kFlatItem / NT;
+    const FlatItem it = a.items[item];
+    const FlatEntry en = a.entries[it.entry];
+    const gptr<float> x = gmut<float>(a.tensors[en.tensor]);
+    const gptr<bf16_t> g = gmut<bf16_t>(src[en.tensor]);
+    const uint32_t cnt = uint32_t(en.numel - it.start < kFlatItem ? en.numel - it.start : kFlatItem);
+    const rsrc_t rx = make_rsrc(static_cast<float*>(a.tensors[en.tensor]) + it.start, cnt * 4u);
+    const rsrc_t rg = make_rsrc(static_cast<bf16_t*>(src[en.tensor]) + it.start, cnt * 2u);
+    const rsrc_t rf = make_rsrc(stage + en.off + it.start, cnt * 4u);
+    const float w = float(a.world);
+    float v[PER], h[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int64_t j = it.start + int64_t(q) * NT + threadIdx.x;
+        const int64_t jc = j < en.numel ? j : 0;  // clamped, unconditional
+        v[q] = x[jc];
+        h[q] = bf2f(g[jc]);
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        keep(v[q]);
+        keep(h[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int64_t j = it.start + int64_t(q) * NT + threadIdx.x;
+        if (j < en.numel) {
+            const uint32_t e = uint32_t(int64_t(q) * NT + threadIdx.x);
+            float t = v[q] + h[q];
+            keep(t);  // the sum the ADD stores, then the pack's division
+            StIo<float>::template st1<kStAuxSlot>(rf, e * 4u, a.world != 1 ? t / w : t);
+            StIo<float>::st1(rx, e * 4u, 0.f);
+            StIo<bf16_t>::st1(rg, e * 2u, 0.f);
+        }
+    }
+}
+
+// Round: flat (bf16) = f2bf(stage), round to nearest even: the run-table GATHER of the three-stage
+// flow on the item's elements of the all-reduced flat tail.
+template <int NT>
+__device__ __forceinline__ void flat_round_item(const FlatArgs& a, const float* stage, int item) {
+    constexpr int PER = kFlatItem / NT;
+    const FlatItem it = a.items[item];
+    const FlatEntry en = a.entries[it.entry];
+    const gptr<const float> x = gconst<float>(stage) + en.off;
+    const uint32_t cnt = uint32_t(en.numel - it.start < kFlatItem ? en.numel - it.start : kFlatItem);
+    const rsrc_t rf = make_rsrc(static_cast<bf16_t*>(a.flat) + en.off + it.start, cnt * 2u);
+    float v[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int64_t j = it.start + int64_t(q) * NT + threadIdx.x;
+        v[q] = x[j < en.numel ? j : 0];  // clamped, unconditional
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) keep(v[q]);
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int64_t j = it.start + int64_t(q) * NT + threadIdx.x;
+        if (j < en.numel) StIo<bf16_t>::st1(rf, uint32_t(int64_t(q) * NT + threadIdx.x) * 2u, v[q]);
+    }
+}
+
 struct TileGeom {
     int lane, wave, L, sub, ql;
     int64_t n, m, row_begin, row_end, first_row;
@@ -1373,6 +1442,26 @@ __global__ __launch_bounds__(kBlock) void k_apply_mix(ApplyArgs a, MixArgs x) {
         apply_tile<float, R, NI, true, 1, ONT, bf16_pin_t>(a, d, t);
 }
 
+// The final pass of psgd_aggregate_mixed_comm at world size > 1: k_apply<float, R, NI, false> (two
+// term sets: the residual from the local factors, the output alpha x the all-reduced ones; the
+// same fp32 arithmetic in the same order) with the output stored as bf16, the flat items as
+// flat_round_item. out_nt is 0 at W > 1: no ONT instance.
+template <int R, int NI>
+__global__ __launch_bounds__(kBlock) void k_apply_mix_w(ApplyArgs a, MixArgs x) {
+    static_assert(R <= 4, "mixed instances: rank buckets 1, 2 and 4");
+    const int nf = a.flat.nitems;
+    if (int(blockIdx.x) < nf) {
+        flat_round_item<kBlock>(a.flat, x.stage, blockIdx.x);
+        return;
+    }
+    const Tile t = a.tiles[blockIdx.x - nf];
+    const MatDesc d = a.mats[t.mat];
+    if (d.vec)
+        apply_tile<float, R, NI, false, 4, false, bf16_pin_t>(a, d, t);
+    else
+        apply_tile<float, R, NI, false, 1, false, bf16_pin_t>(a, d, t);
+}
+
 // resident waves per SIMD of a kernel at NT threads per workgroup; 0 when it uses scratch
 template <typename F>
 hipError_t resident_waves(F fn, int NT, int* waves) {
@@ -1411,6 +1500,39 @@ hipError_t dispatch_apply_mix_r(int nterms, const ApplyArgs& a, const MixArgs& x
         default: PSGD_AM(-1); break;
     }
 #undef PSGD_AM
+    return hipGetLastError();
+}
+
+// W > 1: the instance k_apply's dispatch picks for two term sets (dispatch_apply_r, !shared: rank 4
+// caches up to 3 terms, its 4-term instance spilled), so the mixed pass runs the same NI
+template <int R>
+hipError_t dispatch_apply_mix_w(int nterms, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s,
+                                int* waves) {
+    const dim3 grid(ntiles + a.flat.nitems), block(kBlock);
+    constexpr int kMaxNI = R <= 2 ? 4 : 3;
+    const int NI = nterms <= kMaxNI ? nterms : -1;
+#define PSGD_AW(NN)                                                                          \
+    do {                                                                                     \
+        if (waves) {                                                                         \
+            const hipError_t e = resident_waves(&k_apply_mix_w<R, NN>, kBlock, waves);      \
+            if (e != hipSuccess) return e;                                                   \
+        }                                                                                    \
+        if (ntiles + a.flat.nitems == 0) return hipSuccess;                                  \
+        timed_launch(&k_apply_mix_w<R, NN>, grid, block, s, a, x);                           \
+    } while (0)
+    switch (NI) {
+        case 1: PSGD_AW(1); break;
+        case 2: PSGD_AW(2); break;
+        case 3: PSGD_AW(3); break;
+        case 4:
+            if constexpr (kMaxNI >= 4) {
+                PSGD_AW(4);
+                break;
+            }
+            [[fallthrough]];
+        default: PSGD_AW(-1); break;
+    }
+#undef PSGD_AW
     return hipGetLastError();
 }
 

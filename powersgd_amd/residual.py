@@ -20,8 +20,11 @@ gradients: the two element-wise passes, an fp32 codec step, 4 bytes of state per
 wherever it applies (one process, a compressing step, rank bucket 1 / 2 / 4): the codec's final
 pass stores the bf16 averages itself (no GATHER pass), and where a step is one gradient pass
 (one iteration per step, odd steps) that pass also ingests the bf16 gradients (no ADD pass; on the
-other steps the library launches the ADD). Bit for bit the three-stage flow above; every other
-case runs it.
+other steps the library launches the ADD). In a process group that runs over the library's own RCCL
+communicator the one call is psgd_aggregate_mixed_comm: the output fold on every step, the ADD
+always a launch of the library's, the uncompressed tensors all-reduced in fp32 and rounded in the
+final launch. Bit for bit the three-stage flow above; every other case (``PSGD_COMM=ipc`` /
+``torch``, gloo, an ineligible plan) runs it.
 """
 from __future__ import annotations
 
@@ -99,23 +102,41 @@ class Fp32ResidualPowerSGD(Aggregator):
         self._gather.gather(self._slab.data_ptr(), ctypes.addressof(self._out_ptrs), stream)
         return outs
 
+    def _fused_comm(self):
+        """The library's own communicator when this process group runs over it (``PowerSGD.aggregate``'s
+        choice: RCCL, not ``PSGD_COMM=ipc`` / ``torch``, not gloo), else None. Collective on first use."""
+        codec = self.inner._powersgd
+        if not is_distributed() or codec._ipc_mode():
+            return None
+        return codec._rccl_comm()
+
     def _fused_applies(self) -> bool:
-        """The step about to run compresses, in one process, on a plan psgd_aggregate_mixed serves
-        (both step parities: a plan is eligible or not as a whole)."""
+        """The step about to run compresses, on a plan the one-call form serves (both step parities:
+        a plan is eligible or not as a whole): psgd_aggregate_mixed in one process,
+        psgd_aggregate_mixed_comm in a process group that runs over the library's communicator."""
         inner = self.inner
-        if is_distributed() or inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
+        if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
             return False
         plan = inner._powersgd._plan
+        if is_distributed():
+            comm = self._fused_comm()
+            if comm is None:
+                return False
+            return plan.mixed_folds_comm(0, comm.world)[1] == 1 and plan.mixed_folds_comm(1, comm.world)[1] == 1
         return plan.mixed_folds(0)[1] == 1 and plan.mixed_folds(1)[1] == 1
 
     def fused_folds(self):
         """``(fold_in, fold_out)`` of the NEXT ``aggregate`` call: 1 where the ingest of the bf16
         gradients / the bf16 rounding of the averages will run inside the codec's own gradient
-        pass (psgd_plan_mixed_folds); ``(0, 0)`` whenever that call runs the three-stage flow
-        (``fused=False``, a warm-up step, more than one process, a plan the fused call refuses)."""
+        pass (psgd_plan_mixed_folds; over a communicator psgd_plan_mixed_folds_comm: ``(0, 1)``);
+        ``(0, 0)`` whenever that call runs the three-stage flow (``fused=False``, a warm-up step, a
+        process group on another transport, a plan the fused call refuses)."""
         if not (self.fused and self._fused_applies()):
             return (0, 0)
-        return self.inner._powersgd._plan.mixed_folds(self.inner._powersgd.step_counter)
+        codec = self.inner._powersgd
+        if is_distributed():
+            return codec._plan.mixed_folds_comm(codec.step_counter, self._fused_comm().world)
+        return codec._plan.mixed_folds(codec.step_counter)
 
     def _aggregate_fused(self, gradients: List[torch.Tensor], stream: int) -> List[torch.Tensor]:
         """``PowerSGD.aggregate`` of ``inner`` on the residual, as psgd_aggregate_mixed[_flat]: the
@@ -137,16 +158,19 @@ class Fp32ResidualPowerSGD(Aggregator):
         inner._table.fill(self.views)
         inner.step_counter += 1
         outs = st["comp_slab"].get()
+        comm = self._fused_comm()
+        kw = {}
         if inner._unc is not None:
             unc = st["unc_slab"].get()
-            codec._plan.aggregate_mixed(st["grads"].comp_addr(), inner._table.comp_addr(), st["comp_slab"].data_ptr(),
-                                        codec.step_counter, stream, flat=inner._unc.plan,
-                                        unc_bf16=st["grads"].unc_addr(), unc_residual=inner._table.unc_addr(),
-                                        flat_out=st["unc_slab"].data_ptr())
+            kw = dict(flat=inner._unc.plan, unc_bf16=st["grads"].unc_addr(), unc_residual=inner._table.unc_addr(),
+                      flat_out=st["unc_slab"].data_ptr())
             outs = outs + unc
+        if comm is not None:
+            codec._plan.aggregate_mixed_comm(st["grads"].comp_addr(), inner._table.comp_addr(),
+                                             st["comp_slab"].data_ptr(), codec.step_counter, comm, stream, **kw)
         else:
             codec._plan.aggregate_mixed(st["grads"].comp_addr(), inner._table.comp_addr(), st["comp_slab"].data_ptr(),
-                                        codec.step_counter, stream)
+                                        codec.step_counter, stream, **kw)
         codec.step_counter += 1
         return [outs[i] for i in inner._order]
 

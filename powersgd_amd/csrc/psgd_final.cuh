@@ -749,32 +749,19 @@ hipError_t launch_final_k(const FinalArgs& a, int ntiles, hipStream_t s, int* wa
     constexpr int NT = FinNT<R>::value;
     static_assert(MIX == 0 || std::is_same<T, float>::value, "mixed instances: fp32 plans");
     static_assert(MIX != 2 || (K == 0 && !PJ), "ingest fold: the single-pass form");
-    if (waves) {  // resident waves per SIMD; 0 when the instance spills to scratch
-        const void* fn;
-        if constexpr (MIX != 0 && PJ)
-            fn = reinterpret_cast<const void*>(&k_final_proj_mix<R, SMAX>);
-        else if constexpr (MIX != 0)
-            fn = reinterpret_cast<const void*>(&k_final_odd_mix<R, K, SMAX, MIX == 2>);
-        else if constexpr (PJ)
-            fn = reinterpret_cast<const void*>(&k_final_proj<T, R, SMAX>);
-        else
-            fn = reinterpret_cast<const void*>(&k_final_odd<T, R, K, SMAX>);
-        int blocks = 0;
-        hipFuncAttributes fa{};
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, NT, 0);
-        if (e == hipSuccess) e = hipFuncGetAttributes(&fa, fn);
-        if (e != hipSuccess) return e;
-        *waves = fa.localSizeBytes > 0 ? 0 : blocks * (NT / 64) / 4;
-    }
+    const auto fn = [] {
+        if constexpr (MIX != 0 && PJ) return &k_final_proj_mix<R, SMAX>;
+        else if constexpr (MIX != 0) return &k_final_odd_mix<R, K, SMAX, MIX == 2>;
+        else if constexpr (PJ) return &k_final_proj<T, R, SMAX>;
+        else return &k_final_odd<T, R, K, SMAX>;
+    }();
+    if (waves)
+        if (const hipError_t e = resident_waves(fn, NT, waves); e != hipSuccess) return e;
     if (ntiles == 0) return hipSuccess;
-    if constexpr (MIX != 0 && PJ)
-        timed_launch(&k_final_proj_mix<R, SMAX>, dim3(ntiles + a.flat.nitems), dim3(NT), s, a, *mx);
-    else if constexpr (MIX != 0)
-        timed_launch(&k_final_odd_mix<R, K, SMAX, MIX == 2>, dim3(ntiles + a.flat.nitems), dim3(NT), s, a, *mx);
-    else if constexpr (PJ)
-        timed_launch(&k_final_proj<T, R, SMAX>, dim3(ntiles + a.flat.nitems), dim3(NT), s, a);
+    if constexpr (MIX != 0)
+        timed_launch(fn, dim3(ntiles + a.flat.nitems), dim3(NT), s, a, *mx);
     else
-        timed_launch(&k_final_odd<T, R, K, SMAX>, dim3(ntiles + a.flat.nitems), dim3(NT), s, a);
+        timed_launch(fn, dim3(ntiles + a.flat.nitems), dim3(NT), s, a);
     return hipGetLastError();
 }
 
@@ -849,15 +836,8 @@ hipError_t dispatch_final(int R, int nres, int smax, const FinalArgs& a, int nti
 template <typename T, int SMAX, int K>
 hipError_t launch_oe_k(const FinalArgs& a, int ntiles, hipStream_t s, int* waves) {
     constexpr int NT = FinNT<1>::value;
-    if (waves) {  // resident waves per SIMD; 0 when the instance spills to scratch
-        const void* fn = reinterpret_cast<const void*>(&k_final_oe<T, K, SMAX>);
-        int blocks = 0;
-        hipFuncAttributes fa{};
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, NT, 0);
-        if (e == hipSuccess) e = hipFuncGetAttributes(&fa, fn);
-        if (e != hipSuccess) return e;
-        *waves = fa.localSizeBytes > 0 ? 0 : blocks * (NT / 64) / 4;
-    }
+    if (waves)
+        if (const hipError_t e = resident_waves(&k_final_oe<T, K, SMAX>, NT, waves); e != hipSuccess) return e;
     if (ntiles == 0) return hipSuccess;
     k_final_oe<T, K, SMAX><<<ntiles, NT, 0, s>>>(a);
     return hipGetLastError();
@@ -881,16 +861,18 @@ hipError_t dispatch_final_oe(int nres, int smax, const FinalArgs& a, int ntiles,
     return hipErrorInvalidValue;
 }
 
+// Term counts k_lowrank_out and k_lowrank_mix cache in registers (NI; -1: loaded per use):
+// 1 / 2 / 4 terms at ranks <= 8 (ranks 16 / 32 always run NI = -1)
+constexpr int lowrank_ni(int R, int nterms) {
+    return R <= 8 && (nterms == 1 || nterms == 2 || nterms == 4) ? nterms : -1;
+}
+
 template <typename T, int R>
 hipError_t dispatch_lowrank_r(int nterms, const ApplyArgs& a, int ntiles, hipStream_t s) {
-    const dim3 grid(ntiles), block(kBlock);
-    switch (R <= 8 ? nterms : -1) {
-        case 1: k_lowrank_out<T, R, 1><<<grid, block, 0, s>>>(a); break;
-        case 2: k_lowrank_out<T, R, 2><<<grid, block, 0, s>>>(a); break;
-        case 4: k_lowrank_out<T, R, 4><<<grid, block, 0, s>>>(a); break;
-        default: k_lowrank_out<T, R, -1><<<grid, block, 0, s>>>(a); break;
-    }
-    return hipGetLastError();
+    return by_ni<1, 2, 4>(lowrank_ni(R, nterms), [&](auto N) {
+        k_lowrank_out<T, R, decltype(N)::value><<<ntiles, kBlock, 0, s>>>(a);
+        return hipGetLastError();
+    });
 }
 
 template <typename T>

@@ -314,12 +314,12 @@ int psgd_aggregate_ipc(psgd_plan* p, void* const* grads, void* out, int64_t step
         return fail(PSGD_ERR_STATE, "an earlier IPC exchange wait timed out (a peer did not arrive within "
                                     "PSGD_IPC_SPIN); the exchange is invalid until psgd_ipc_close");
     if (step < 0 || step >= 0xffffffffLL) return fail(PSGD_ERR_VALUE, "step out of range (epochs are 32-bit)");
-    if (reinterpret_cast<uintptr_t>(out) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    if (int st = check_out(out)) return st;
     const bool has_flat = f && f->total > 0;
     if (has_flat) {
-        if (!unc || !flat_out) return fail(PSGD_ERR_VALUE, "null argument");
-        if (!f->bound) return fail(PSGD_ERR_STATE, "flat plan is not bound");
-        if (f->dtype != PSGD_F32) return fail(PSGD_ERR_DTYPE, "psgd_aggregate_ipc packs fp32 uncompressed tensors");
+        if (int st = check_flat(f, unc && flat_out, f->dtype == PSGD_F32, PSGD_ERR_DTYPE,
+                                "psgd_aggregate_ipc packs fp32 uncompressed tensors"))
+            return st;
         if (f->total > p->ipc_flat_cap) return fail(PSGD_ERR_VALUE, "flat tensors exceed the exchange buffer (psgd_ipc_create)");
     }
     DevScope scope(p->device);

@@ -32,9 +32,31 @@ const char* ineligible(const psgd_plan* p) {
     return nullptr;
 }
 
-bool admitted(hipError_t e, int waves) { return e == hipSuccess && waves >= 2; }
+// the context psgd_aggregate_mixed runs its step under (aggregate_ctx)
+StepCtx mixed_ctx(const MixArgs* x, bool ingest) {
+    StepCtx c;
+    c.mix = x;
+    c.mix_in = ingest;
+    return world1_ctx(c);
+}
 
-// (Re-)ask the runtime about the mixed instances this plan's current tiling would launch
+// Admission: the runtime keeps at least two waves per SIMD of the instance a route's final pass
+// would launch, without scratch (asked through the launch functions the drivers use)
+bool admitted(hipError_t e, int waves) { return e == hipSuccess && waves >= 2; }
+bool admitted(const psgd_plan* p, const IterRoute& r, const MixArgs& none) {
+    int w = 0;
+    return admitted(launch_final_pass(p, r, FinalArgs{}, &none, 0, nullptr, &w), w);
+}
+bool admitted(const psgd_plan* p, const OutRoute& o, const MixArgs& none) {
+    int w = 0;
+    ApplyArgs aa{};
+    return admitted(launch_out_pass(p, o, aa, &none, 0, nullptr, &w), w);
+}
+
+// (Re-)ask the runtime about the mixed instances this plan's current tiling would launch: per
+// step parity its final pass, and its first pass where that is the single-pass ingest instance.
+// The key covers every plan field the routes read that can change after creation (a re-tiling:
+// fin_ok, fin_proj, oe_ok, fin_smax, out_nt); rank bucket, iterations and the knobs are fixed
 void admit(psgd_plan* p) {
     psgd_plan::Mixed& m = *p->mixed;
     const uint64_t key = uint64_t(p->fin_ok) | uint64_t(p->fin_proj) << 1 | uint64_t(p->oe_ok) << 2 |
@@ -42,30 +64,19 @@ void admit(psgd_plan* p) {
     if (m.key == key) return;
     m.key = key;
     const MixArgs none{};
-    int w = 0;
-    const int smax = fin_bucket(p->fin_smax);
     m.fin_in = false;
-    if (p->mix_ingest_on && p->iters == 1 && p->fused_final(1, true) && smax > 0) {
-        w = 0;
-        m.fin_in = admitted(launch_final_mix(p->rbucket, 0, smax, true, FinalArgs{}, none, 0, nullptr, &w), w);
-    }
-    for (int par = 0; par < 2; ++par) {  // the final pass of a step of this parity
-        w = 0;
-        if (p->fused_final(par, true)) {
-            const int nres = p->proj_final(par, true) ? kFinProj : p->iters - 1;
-            m.out[par] = smax > 0 && admitted(launch_final_mix(p->rbucket, nres, smax, false, FinalArgs{}, none, 0, nullptr, &w), w);
-        } else {
-            ApplyArgs aa{};
-            aa.out_nt = p->out_nt;
-            m.out[par] = admitted(launch_apply_mix(p->rbucket, p->iters, aa, none, 0, nullptr, &w), w);
-        }
+    for (int par = 0; par < 2; ++par) {
+        const IterRoute first = p->route(par, 0, mixed_ctx(&none, p->mix_ingest_on));
+        if (first.pass == IterRoute::PassFinal && first.ingest) m.fin_in = admitted(p, first, none);
+        const StepCtx c = mixed_ctx(&none, false);
+        const IterRoute last = p->route(par, p->iters - 1, c);
+        m.out[par] = last.pass == IterRoute::PassFinal ? admitted(p, last, none) : admitted(p, p->out_route(par, 1, c), none);
     }
 }
 
-// psgd_aggregate_mixed_comm: the bf16-output instance of the step's final pass as
-// aggregate_comm_ctx / decompress_impl pick it: after a fused k_final_odd (fin_ok, the last
-// iteration odd) the output pass k_lowrank_mix; else k_apply_mix_w (two term sets, W > 1) or, with
-// a 1-rank communicator, the world-size-1 k_apply_mix
+// psgd_aggregate_mixed_comm: the bf16-output instance of the output pass, per communicator kind
+// ([0]: world size > 1, [1]: a 1-rank communicator) and step parity. Its routes read fin_ok and
+// out_nt of what a re-tiling can change: the key
 void admit_comm(psgd_plan* p) {
     psgd_plan::Mixed& m = *p->mixed;
     const uint64_t key = uint64_t(p->fin_ok) | uint64_t(uint32_t(p->out_nt)) << 8;
@@ -73,20 +84,8 @@ void admit_comm(psgd_plan* p) {
     m.comm_key = key;
     const MixArgs none{};
     for (int one = 0; one < 2; ++one)
-        for (int par = 0; par < 2; ++par) {
-            int w = 0;
-            ApplyArgs aa{};
-            hipError_t e;
-            if (p->fused_final(par, false)) {
-                e = launch_lowrank_mix(p->rbucket, p->iters, aa, none, 0, nullptr, &w);
-            } else if (one) {
-                aa.out_nt = p->out_nt;
-                e = launch_apply_mix(p->rbucket, p->iters, aa, none, 0, nullptr, &w);
-            } else {
-                e = launch_apply_mix_w(p->rbucket, p->iters, aa, none, 0, nullptr, &w);
-            }
-            m.comm_out[one][par] = admitted(e, w);
-        }
+        for (int par = 0; par < 2; ++par)
+            m.comm_out[one][par] = admitted(p, p->out_route(par, one ? 1 : 2, comm_out_ctx(&none)), none);
 }
 
 bool comm_eligible(const psgd_plan* p, int world) {
@@ -124,7 +123,9 @@ int ensure(psgd_plan* p) {
 void folds_at(const psgd_plan* p, int64_t step, int32_t* in, int32_t* out) {
     const psgd_plan::Mixed& m = *p->mixed;
     const bool eligible = m.out[0] && m.out[1];
-    const bool single = p->iters == 1 && !p->even(step, 0) && p->fused_final(step, true);
+    // the step's only gradient pass is the single-pass final kernel
+    const IterRoute first = p->route(step, 0, mixed_ctx(nullptr, true));
+    const bool single = first.pass == IterRoute::PassFinal && first.ingest;
     *out = eligible ? 1 : 0;
     *in = eligible && single && m.fin_in ? 1 : 0;
 }
@@ -149,15 +150,38 @@ int unc_table(psgd_plan::Mixed& m, psgd_flat* f, void* const* unc, void* const* 
     return PSGD_OK;
 }
 
-int mixed_impl(psgd_plan* p, void* const* grads, void* const* residual, void* out, int64_t step, psgd_flat* f,
-               void* const* unc, void* const* unc_residual, void* flat_out, hipStream_t s) {
+// the plan's eligibility, then every tensor's two pointers
+int check_tensors(const psgd_plan* p, void* const* grads, void* const* residual) {
     if (const char* why = ineligible(p)) return fail(PSGD_ERR_VALUE, why);
-    const size_t nt = p->shapes.size();
-    for (size_t i = 0; i < nt; ++i) {
+    for (size_t i = 0; i < p->shapes.size(); ++i) {
         if (!grads[i] || !residual[i]) return fail(PSGD_ERR_VALUE, "null gradient pointer");
         if (reinterpret_cast<uintptr_t>(grads[i]) % 2) return fail(PSGD_ERR_LAYOUT, "bf16 gradients must be 2-byte aligned");
         if (reinterpret_cast<uintptr_t>(residual[i]) % 4) return fail(PSGD_ERR_LAYOUT, "the fp32 residual must be 4-byte aligned");
     }
+    return PSGD_OK;
+}
+
+// A fold query: admission is a property of this build's kernels on the device (asked once per
+// tiling); the query caches it in the plan like the first mixed call does. A plan with no device
+// yet asks without keeping device state (a temporary Mixed for the duration of the query).
+template <typename Read>
+int query_folds(const psgd_plan* plan, void (*admit_fn)(psgd_plan*), Read read) {
+    psgd_plan* p = const_cast<psgd_plan*>(plan);
+    DevScope scope(p->device);
+    psgd_plan::Mixed tmp;
+    const bool unbound = !p->mixed && !p->bound;
+    if (unbound) p->mixed = &tmp;
+    if (!p->mixed)
+        if (int st = ensure(p)) return st;
+    admit_fn(p);
+    read(p);
+    if (unbound) p->mixed = nullptr;
+    return PSGD_OK;
+}
+
+int mixed_impl(psgd_plan* p, void* const* grads, void* const* residual, void* out, int64_t step, psgd_flat* f,
+               void* const* unc, void* const* unc_residual, void* flat_out, hipStream_t s) {
+    if (int st = check_tensors(p, grads, residual)) return st;
     DevScope scope(p->device);
     if (int st = ensure(p)) return st;
     psgd_plan::Mixed& m = *p->mixed;
@@ -183,11 +207,9 @@ int mixed_impl(psgd_plan* p, void* const* grads, void* const* residual, void* ou
     } else {
         if (int st = psgd_runs_add_list(m.add, grads, residual, 1, s)) return st;
     }
-    StepCtx c;
+    StepCtx c = mixed_ctx(&x, in != 0);
     c.fl = f ? &fa : nullptr;
     c.out = out;
-    c.mix = &x;
-    c.mix_in = in != 0;
     return aggregate_ctx(p, residual, step, s, c);
 }
 
@@ -248,41 +270,21 @@ int psgd_plan_mixed_folds(const psgd_plan* plan, int64_t step, int32_t* fold_in,
     if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
     *fold_in = *fold_out = 0;
     if (ineligible(plan)) return PSGD_OK;
-    // admission is a property of this build's kernels on the device (asked once per tiling); the
-    // query caches it in the plan like the first mixed call does
-    psgd_plan* p = const_cast<psgd_plan*>(plan);
-    DevScope scope(p->device);
-    if (!p->mixed) {
-        if (!p->bound) {  // no device yet: ask without keeping device state
-            psgd_plan::Mixed tmp;
-            p->mixed = &tmp;
-            admit(p);
-            folds_at(p, step, fold_in, fold_out);
-            p->mixed = nullptr;
-            return PSGD_OK;
-        }
-        if (int st = ensure(p)) return st;
-    }
-    admit(p);
-    folds_at(p, step, fold_in, fold_out);
-    return PSGD_OK;
+    return query_folds(plan, admit, [&](const psgd_plan* p) { folds_at(p, step, fold_in, fold_out); });
 }
 
 int psgd_aggregate_mixed_flat(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,
                               psgd_flat* f, void* const* unc_bf16, void* const* unc_residual, void* flat_out_bf16,
                               void* stream) {
-    if (!p || !grads_bf16 || !residual || !out_bf16) return fail(PSGD_ERR_VALUE, "null argument");
-    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
-    if (reinterpret_cast<uintptr_t>(out_bf16) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    if (int st = check_call(p && grads_bf16 && residual && out_bf16, p && p->bound, step >= 0, "step out of range"))
+        return st;
+    if (int st = check_out(out_bf16)) return st;
     const bool has_flat = f && f->total > 0;
-    if (has_flat) {
-        if (!unc_bf16 || !unc_residual || !flat_out_bf16) return fail(PSGD_ERR_VALUE, "null argument");
-        if (!f->bound) return fail(PSGD_ERR_STATE, "flat plan is not bound");
-        if (f->dtype != PSGD_F32 || f->device != p->device)
-            return fail(PSGD_ERR_VALUE, "psgd_aggregate_mixed_flat takes an fp32 flat plan (the uncompressed tensors' "
-                                        "residual) on the codec's device");
-    }
+    if (has_flat)
+        if (int st = check_flat(f, unc_bf16 && unc_residual && flat_out_bf16, f->dtype == PSGD_F32 && f->device == p->device,
+                                PSGD_ERR_VALUE, "psgd_aggregate_mixed_flat takes an fp32 flat plan (the uncompressed tensors' "
+                                                "residual) on the codec's device"))
+            return st;
     return mixed_impl(p, grads_bf16, residual, out_bf16, step, has_flat ? f : nullptr, unc_bf16, unc_residual,
                       flat_out_bf16, static_cast<hipStream_t>(stream));
 }
@@ -294,45 +296,22 @@ int psgd_plan_mixed_folds_comm(const psgd_plan* plan, int64_t step, int32_t worl
     if (world < 1) return fail(PSGD_ERR_VALUE, "world size must be >= 1");
     *fold_in = *fold_out = 0;  // no ingest fold in this form: the ADD is always a launch of its own
     if (ineligible(plan)) return PSGD_OK;
-    psgd_plan* p = const_cast<psgd_plan*>(plan);
-    DevScope scope(p->device);
-    if (!p->mixed) {
-        if (!p->bound) {  // no device yet: ask without keeping device state
-            psgd_plan::Mixed tmp;
-            p->mixed = &tmp;
-            admit_comm(p);
-            *fold_out = comm_eligible(p, world) ? 1 : 0;
-            p->mixed = nullptr;
-            return PSGD_OK;
-        }
-        if (int st = ensure(p)) return st;
-    }
-    admit_comm(p);
-    *fold_out = comm_eligible(p, world) ? 1 : 0;
-    return PSGD_OK;
+    return query_folds(plan, admit_comm, [&](const psgd_plan* p) { *fold_out = comm_eligible(p, world) ? 1 : 0; });
 }
 
 int psgd_aggregate_mixed_comm(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16,
                               int64_t step, psgd_flat* f, void* const* unc_bf16, void* const* unc_residual,
                               void* flat_out_bf16, psgd_comm* comm, void* stream) {
-    if (!p || !grads_bf16 || !residual || !out_bf16 || !comm) return fail(PSGD_ERR_VALUE, "null argument");
-    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
-    if (reinterpret_cast<uintptr_t>(out_bf16) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    if (int st = check_call(p && grads_bf16 && residual && out_bf16 && comm, p && p->bound, step >= 0, "step out of range"))
+        return st;
+    if (int st = check_out(out_bf16)) return st;
     const bool has_flat = f && f->total > 0;
-    if (has_flat) {
-        if (!unc_bf16 || !unc_residual || !flat_out_bf16) return fail(PSGD_ERR_VALUE, "null argument");
-        if (!f->bound) return fail(PSGD_ERR_STATE, "flat plan is not bound");
-        if (f->dtype != PSGD_F32 || f->device != p->device)
-            return fail(PSGD_ERR_VALUE, "psgd_aggregate_mixed_comm takes an fp32 flat plan (the uncompressed tensors' "
-                                        "residual) on the codec's device");
-    }
-    if (const char* why = ineligible(p)) return fail(PSGD_ERR_VALUE, why);
-    for (size_t i = 0; i < p->shapes.size(); ++i) {
-        if (!grads_bf16[i] || !residual[i]) return fail(PSGD_ERR_VALUE, "null gradient pointer");
-        if (reinterpret_cast<uintptr_t>(grads_bf16[i]) % 2) return fail(PSGD_ERR_LAYOUT, "bf16 gradients must be 2-byte aligned");
-        if (reinterpret_cast<uintptr_t>(residual[i]) % 4) return fail(PSGD_ERR_LAYOUT, "the fp32 residual must be 4-byte aligned");
-    }
+    if (has_flat)
+        if (int st = check_flat(f, unc_bf16 && unc_residual && flat_out_bf16, f->dtype == PSGD_F32 && f->device == p->device,
+                                PSGD_ERR_VALUE, "psgd_aggregate_mixed_comm takes an fp32 flat plan (the uncompressed tensors' "
+                                                "residual) on the codec's device"))
+            return st;
+    if (int st = check_tensors(p, grads_bf16, residual)) return st;
     // a poisoned communicator is refused before the step launches anything: the caller's
     // gradients, the residual and the P/Q state stay as they were
     std::string why;

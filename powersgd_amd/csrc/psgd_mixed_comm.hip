@@ -28,24 +28,14 @@ __global__ __launch_bounds__(kBlock) void k_lowrank_mix(ApplyArgs a, MixArgs x) 
 template <int R>
 hipError_t dispatch_lowrank_mix(int nterms, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s,
                                 int* waves) {
-    const dim3 grid(ntiles + a.flat.nitems), block(kBlock);
-#define PSGD_LM(NN)                                                                      \
-    do {                                                                                 \
-        if (waves) {                                                                     \
-            const hipError_t e = resident_waves(&k_lowrank_mix<R, NN>, kBlock, waves);  \
-            if (e != hipSuccess) return e;                                               \
-        }                                                                                \
-        if (ntiles + a.flat.nitems == 0) return hipSuccess;                              \
-        k_lowrank_mix<R, NN><<<grid, block, 0, s>>>(a, x);                               \
-    } while (0)
-    switch (nterms) {  // the term counts dispatch_lowrank_r caches
-        case 1: PSGD_LM(1); break;
-        case 2: PSGD_LM(2); break;
-        case 4: PSGD_LM(4); break;
-        default: PSGD_LM(-1); break;
-    }
-#undef PSGD_LM
-    return hipGetLastError();
+    return by_ni<1, 2, 4>(lowrank_ni(R, nterms), [&](auto N) -> hipError_t {
+        const auto fn = &k_lowrank_mix<R, decltype(N)::value>;
+        if (waves)
+            if (const hipError_t e = resident_waves(fn, kBlock, waves); e != hipSuccess) return e;
+        if (ntiles + a.flat.nitems == 0) return hipSuccess;
+        fn<<<ntiles + a.flat.nitems, kBlock, 0, s>>>(a, x);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_lowrank_mix(int R, int nterms, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s,

@@ -366,7 +366,10 @@ int psgd_plan_bucket_range(const psgd_plan* p, int32_t b, int64_t* p_off, int64_
 int psgd_plan_fused_final(const psgd_plan* p, int64_t step, int32_t aggregate, int32_t* fused) {
     if (!p || !fused) return fail(PSGD_ERR_VALUE, "null argument");
     if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
-    *fused = p->proj_final(step, aggregate != 0) ? 2 : p->fused_final(step, aggregate != 0) ? 1 : 0;
+    StepCtx c;
+    c.fuse = c.write_out = aggregate != 0;
+    const IterRoute r = p->route(step, p->iters - 1, c);
+    *fused = r.pass != IterRoute::PassFinal ? 0 : r.proj ? 2 : 1;
     return PSGD_OK;
 }
 
@@ -379,7 +382,7 @@ int psgd_plan_is_wide(const psgd_plan* p, int32_t* out) {
 int psgd_plan_odd_even(const psgd_plan* p, int64_t step, int32_t it, int32_t* on) {
     if (!p || !on) return fail(PSGD_ERR_VALUE, "null argument");
     if (step < 0 || it < 0 || it >= p->iters) return fail(PSGD_ERR_VALUE, "step/iteration out of range");
-    *on = p->oe_at(step, it, true) && p->fused_norm(true, it) ? 1 : 0;  // psgd_aggregate folds the norm
+    *on = p->route(step, it, world1_ctx(StepCtx{})).pass == IterRoute::PassOddEven ? 1 : 0;  // psgd_aggregate's step
     return PSGD_OK;
 }
 

@@ -1,9 +1,14 @@
 // Host-side definitions shared by the units behind the C ABI of include/psgd.h:
 //   psgd_geometry.cpp  tile geometry, segmentation, work-list capacities and the workspace carve
 //   psgd_plan.cpp      plan lifecycle: create, queries, bind, buckets, timing
-//   psgd_step.cpp      step drivers and the reducer building blocks
+//   psgd_step.cpp      step drivers (one stage function per IterRoute pass), the final-pass launch
+//                      functions shared with admission, and the reducer building blocks
+//   psgd_mixed.cpp     psgd_aggregate_mixed[_comm]: admission of the mixed instances, fold queries
 //   psgd_ipc.cpp       the IPC exchange arena and psgd_aggregate_ipc
 //   psgd_flat.cpp      flat pack and DDP run tables
+//   psgd_comm.cpp      the communicator behind psgd_aggregate_comm
+// Here: the plan, the per-call StepCtx, and the step route (IterRoute / OutRoute, psgd_plan::route /
+// out_route at the end of this file): the one place that decides what an iteration launches.
 // No torch: plain pointers, hipStream_t as void*. Never included by device code.
 #pragma once
 
@@ -192,6 +197,12 @@ constexpr int kMaxBuckets = 8;
 
 int fin_bucket(int s);  // kernel instance (segments per row) serving s segments; 0: none
 
+}  // namespace psgd
+
+namespace psgd {
+struct StepCtx;
+struct IterRoute;
+struct OutRoute;
 }  // namespace psgd
 
 using namespace psgd;  // the opaque C types below are global (include/psgd.h)
@@ -403,6 +414,12 @@ struct psgd_plan {
     void layout(int num_tensors);  // capacities, first tiling, workspace carve (once, at create)
     int upload_tiles() const;      // every list set_vec / set_f64_tiles rebuilds
 
+    // What a step launches (the step route, below psgd::StepCtx): the drivers, the admission of
+    // the mixed instances and the plan queries all read these two; nothing else decides a launch
+    IterRoute route(int64_t step, int it, const StepCtx& c) const;
+    OutRoute out_route(int64_t step, int world, const StepCtx& c) const;
+
+    // The vocabulary route() / out_route() are written in (psgd_geometry.cpp sets the flags):
     // the last iteration of `step` runs fused (odd, and every matrix fits); `agg`: the caller
     // is psgd_aggregate (world size 1, output written), where the projection form also applies
     bool fused_final(int64_t step, bool agg) const { return (fin_ok || (agg && fin_proj)) && !even(step, iters - 1); }
@@ -476,6 +493,82 @@ struct StepCtx {
     bool mix_in = false;
 };
 
+// The contexts of the two one-call steps, shared by the drivers and by admission (psgd_mixed.cpp):
+// aggregate_ctx runs its iterations and output pass under world1_ctx(c); aggregate_comm_ctx its
+// output pass under comm_out_ctx(mix) (its iterations under a plain StepCtx with the flat fold)
+inline StepCtx world1_ctx(StepCtx c) {
+    c.fuse = c.write_out = true;
+    return c;
+}
+inline StepCtx comm_out_ctx(const MixArgs* mix) {
+    StepCtx c;
+    c.mix = mix;
+    return c;
+}
+
+// The argument checks the step entry points of the C ABI share, in their order
+inline int check_call(bool args, bool bound, bool range, const char* range_msg) {
+    if (!args) return fail(PSGD_ERR_VALUE, "null argument");
+    if (!bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
+    if (!range) return fail(PSGD_ERR_VALUE, range_msg);
+    return PSGD_OK;
+}
+inline int check_out(const void* out) {
+    if (reinterpret_cast<uintptr_t>(out) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    return PSGD_OK;
+}
+// ... and of a flat plan riding in a communicator step: `type_ok` with its own code and message
+inline int check_flat(const psgd_flat* f, bool args, bool type_ok, int type_code, const char* type_msg) {
+    if (!args) return fail(PSGD_ERR_VALUE, "null argument");
+    if (!f->bound) return fail(PSGD_ERR_STATE, "flat plan is not bound");
+    if (!type_ok) return fail(type_code, type_msg);
+    return PSGD_OK;
+}
+
+// ------------------------------------------------------------------ step route ------
+// What iteration `it` of `step` launches under a caller's StepCtx (fp32 / bf16 plans up to rank
+// 32; fp64 and wide plans have no fused forms and one fixed sequence). Plain data from plan flags
+// and the context: compress_impl launches what it says, admission (psgd_mixed.cpp) asks the
+// runtime about the instances it names, the plan queries report it.
+struct IterRoute {
+    bool even;
+    // the in-factor's orthonormalisation: folded into the neighbouring kernels (rank-1 joint norm),
+    // a launch of its own (k_orth_*), or k_orth_chain on Gram partials left by the reduction /
+    // the exchange
+    enum Orth { OrthFolded, OrthLaunch, OrthChain } orth;
+    // the gradient pass: k_even + k_reduce; k_product_odd / k_odd_mfma + k_reduce; k_final_oe (this
+    // odd iteration and the next even product in one pass, no reduction); the fused last iteration
+    // k_final_odd / k_final_proj; no product launch (k_reduce over the odd-even pass's partials)
+    enum Pass { PassEven, PassOdd, PassOddEven, PassFinal, PassFromOddEven } pass;
+    bool fused, fused0;        // rank-1 norm fold: in-factor from the previous reduction / iteration 0
+    bool proj, own_kt;         // PassFinal: projection form; the K-term form on its own row blocks
+    int final_nres;            // PassFinal: kFinProj or `it`
+    bool ingest;               // PassFinal of psgd_aggregate_mixed: the single-pass ingest instance
+    bool chain_from_exchange;  // OrthChain reads history slot 2 (the exchange's sum) instead of slot 1
+    bool prev_after_oe;        // the in-factor's sums of squares / ranges were left after an odd-even pass
+    bool ss_out, gram_out;     // what this iteration's reduction leaves for the next one
+};
+
+// The output pass after the iterations
+struct OutRoute {
+    enum Kind { None /* the fused last iteration wrote the output */, Lowrank, Apply } kind;
+    enum Inst { Plain, Mix /* bf16 output, shared terms */, MixW /* bf16 output, two term sets */ } inst;
+    bool shared;      // world size 1: the all-reduced factors are the local ones
+    int32_t out_nt;   // output stores nt only (world size 1, large plans)
+    bool timed;       // benchmark timing covers this launch
+    bool flat;        // the context's flat items ride in the launch (k_lowrank_out takes none)
+    int reduced_slot; // history slot of the earlier iterations' reduced factors (1: never copied to 2)
+};
+
+// psgd_step.cpp: the final pass of a route, for launching (the drivers) and for asking (admission:
+// ntiles = 0, empty arguments, `*waves` receives the resident waves per SIMD of the instance that
+// would run, 0 with scratch; only the fused and the mixed instances answer). `mix` null: the
+// gradient type's own instance. launch_out_pass stamps the route's out_nt into `a`.
+hipError_t launch_final_pass(const psgd_plan* p, const IterRoute& r, const FinalArgs& a, const MixArgs* mix, int ntiles,
+                             hipStream_t s, int* waves);
+hipError_t launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArgs& a, const MixArgs* mix, int ntiles,
+                           hipStream_t s, int* waves);
+
 // psgd_step.cpp
 int refresh_pointers(psgd_plan* p, void* const* grads, hipStream_t stream);
 int compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s, StepCtx c);
@@ -494,3 +587,52 @@ int aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step
                        void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix);
 
 }  // namespace psgd
+
+inline IterRoute psgd_plan::route(int64_t step, int it, const StepCtx& c) const {
+    IterRoute r{};
+    r.even = even(step, it);
+    r.fused = fused_norm(c.fuse, it);
+    // rank 1, iteration 0, even: the joint norm of the (raw) state P is folded into the even
+    // product (per-chunk sums of squares) and its reduction (divide, write normalised P)
+    r.fused0 = rbucket == 1 && it == 0 && r.even && !fused_final_at(step, it, c.write_out);
+    // projection form of the fused last iteration: its orthonormalisation leaves R' in o_rq
+    r.proj = it == iters - 1 && proj_final(step, c.write_out);
+    // folded orthonormalisation of the projection form: the even reduction leaves Gram partials
+    // and k_orth_chain (no Gram pass, panel rows over several workgroups) replaces k_orth_chol
+    const bool qf = qfold(step, c.write_out);
+    r.chain_from_exchange = c.xgram && it == 1 && !r.even;  // the exchange left the summed Q's Gram
+    r.orth = (qf && r.proj) || r.chain_from_exchange ? IterRoute::OrthChain
+             : !r.fused && !r.fused0                 ? IterRoute::OrthLaunch
+                                                     : IterRoute::OrthFolded;
+    // after an odd-even pass the previous even reduction ran over its own item list
+    r.prev_after_oe = !r.even && it >= 2 && oe_at(step, it - 2, c.write_out) && fused_norm(c.fuse, it - 2);
+    if (r.fused && c.span == nullptr && oe_at(step, it, c.write_out))
+        r.pass = IterRoute::PassOddEven;
+    else if (fused_final_at(step, it, c.write_out))
+        r.pass = IterRoute::PassFinal;
+    else if (r.even && it >= 1 && c.span == nullptr && oe_at(step, it - 1, c.write_out) && fused_norm(c.fuse, it - 1))
+        r.pass = IterRoute::PassFromOddEven;
+    else
+        r.pass = r.even ? IterRoute::PassEven : IterRoute::PassOdd;
+    r.own_kt = !r.proj && !tiles_fin_kt.empty();
+    r.final_nres = r.proj ? kFinProj : it;
+    r.ingest = c.mix_in && it == 0;
+    r.ss_out = fused_norm(c.fuse, it + 1) && it + 1 < iters;
+    r.gram_out = qf && r.even && it + 2 == iters;  // the Q panels' Gram for k_orth_chain
+    return r;
+}
+
+inline OutRoute psgd_plan::out_route(int64_t step, int world, const StepCtx& c) const {
+    OutRoute o{};
+    // after a fused last iteration the residual is written: output only, or (psgd_aggregate at
+    // world size 1, which wrote the output too) nothing
+    o.kind = !fused_final(step, c.write_out) ? OutRoute::Apply : c.write_out ? OutRoute::None : OutRoute::Lowrank;
+    o.inst = !c.mix ? OutRoute::Plain : o.kind == OutRoute::Apply && world > 1 ? OutRoute::MixW : OutRoute::Mix;
+    o.shared = world == 1;
+    o.out_nt = world == 1 ? out_nt : 0;
+    o.timed = o.kind == OutRoute::Apply;
+    o.flat = o.kind == OutRoute::Apply || c.mix != nullptr;
+    // fused (world size 1): the reduced factor was never copied to history slot 2
+    o.reduced_slot = fused_norm(c.fuse, 1) ? 1 : 2;
+    return o;
+}

@@ -67,14 +67,21 @@ int refresh_pointers(psgd_plan* p, void* const* grads, hipStream_t stream) {
 
 namespace {
 
-void fill_terms(const psgd_plan* p, int64_t step, int count, Terms& res) {
+// The first `count` rank-r terms of a step from the factor history: iteration j's in-factor x(j)
+// and out-factor y(j); even -> (P_j = X_j, Q_j = Y_j), odd -> (P_j = Y_j, Q_j = X_j). The output
+// terms of the three decompress drivers take the all-reduced out-factor for y
+template <typename TermsT, typename X, typename Y>
+void fill_terms(const psgd_plan* p, int64_t step, int count, TermsT& res, X x, Y y) {
     for (int j = 0; j < count; ++j) {
         const bool e = p->even(step, j);
-        // local rank-r term of iteration j: even -> (P_j = X_j, Q_j = Y_j); odd -> (P_j = Y_j, Q_j = X_j)
-        res.p[j] = e ? p->hist(0, j) : p->hist(1, j);
-        res.q[j] = e ? p->hist(1, j) : p->hist(0, j);
+        res.p[j] = e ? x(j) : y(j);
+        res.q[j] = e ? y(j) : x(j);
     }
     for (int j = count; j < kMaxTerms; ++j) res.p[j] = res.q[j] = nullptr;
+}
+// the local terms (error feedback): history slots 0 and 1
+void fill_terms(const psgd_plan* p, int64_t step, int count, Terms& res) {
+    fill_terms(p, step, count, res, [p](int j) { return p->hist(0, j); }, [p](int j) { return p->hist(1, j); });
 }
 
 // Timing (benchmarks): HIP events of the final pass (k_apply, or the fused final odd kernel):
@@ -111,12 +118,7 @@ int timing_begin(psgd_plan* p, hipStream_t s, std::pair<hipEvent_t, hipEvent_t>*
 // the in-factor (saving the all-reduced values of the previous iteration), product with
 // G_k formed on the fly, and for even iterations the fixed-order partial reduction.
 void fill_terms64(const psgd_plan* p, int64_t step, int count, TermsF64& res) {
-    for (int j = 0; j < count; ++j) {
-        const bool e = p->even(step, j);
-        res.p[j] = e ? p->hist64(0, j) : p->hist64(1, j);
-        res.q[j] = e ? p->hist64(1, j) : p->hist64(0, j);
-    }
-    for (int j = count; j < kMaxTerms; ++j) res.p[j] = res.q[j] = nullptr;
+    fill_terms(p, step, count, res, [p](int j) { return p->hist64(0, j); }, [p](int j) { return p->hist64(1, j); });
 }
 
 int compress_f64(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s) {
@@ -164,12 +166,8 @@ int decompress_f64(psgd_plan* p, void* const* grads, void* out, int64_t step, in
     a.out = out;
     fill_terms64(p, step, I, a.res);
     double* last = reinterpret_cast<double*>(p->even(step, I - 1) ? p->Q : p->P);
-    for (int k = 0; k < I; ++k) {
-        const bool e = p->even(step, k);
-        double* ybar = k + 1 < I ? p->hist64(2, k) : last;  // all-reduced factor of iteration k
-        a.apx.p[k] = e ? p->hist64(0, k) : ybar;
-        a.apx.q[k] = e ? ybar : p->hist64(0, k);
-    }
+    fill_terms(p, step, I, a.apx, [&](int k) { return p->hist64(0, k); },
+               [&](int k) { return k + 1 < I ? p->hist64(2, k) : last; });  // all-reduced factor of iteration k
     a.nres = I;
     a.alpha = 1.0 / double(world);  // reference alpha = 1 / num_workers (:218)
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
@@ -228,13 +226,8 @@ int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, i
     a.out = out;
     fill_terms(p, step, I, a.res);
     float* last = p->even(step, I - 1) ? p->Q : p->P;  // all-reduced factor of the last iteration
-    for (int k = 0; k < kMaxTerms; ++k) a.apx.p[k] = a.apx.q[k] = nullptr;
-    for (int k = 0; k < I; ++k) {
-        const bool e = p->even(step, k);
-        float* ybar = k + 1 < I ? p->hist(2, k) : last;
-        a.apx.p[k] = e ? p->hist(0, k) : ybar;
-        a.apx.q[k] = e ? ybar : p->hist(0, k);
-    }
+    fill_terms(p, step, I, a.apx, [&](int k) { return p->hist(0, k); },
+               [&](int k) { return k + 1 < I ? p->hist(2, k) : last; });
     a.nres = I;
     a.alpha = float(1.0 / double(world));  // reference alpha = 1 / num_workers (:218)
     a.shared = world == 1 ? 1 : 0;         // the all-reduced factors are the local ones
@@ -301,210 +294,254 @@ int even_stamps_end(psgd_plan* p, const ProductArgs& pa, hipStream_t s) {
 
 }  // namespace
 
-int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s, StepCtx c) {
-    if (p->f64()) return compress_f64(p, grads, step, it, s);
-    if (p->wide()) return compress_wide(p, grads, step, it, s);
-    if (int st = refresh_pointers(p, grads, s)) return st;
-    const psgd_plan::Span sp = c.span ? *c.span : p->full_span();
-    const bool even = p->even(step, it);
-    float* in = even ? p->P : p->Q;
-    float* out = even ? p->Q : p->P;
-    const bool fused = p->fused_norm(c.fuse, it);
-    // rank 1, iteration 0, even: the joint norm of the (raw) state P is folded into the even
-    // product (per-chunk sums of squares) and its reduction (divide, write normalised P)
-    const bool fused0 = p->rbucket == 1 && it == 0 && even && !p->fused_final_at(step, it, c.write_out);
-    // projection form of the fused last iteration: its orthonormalisation leaves R' in o_rq
-    const bool proj = it == p->iters - 1 && p->proj_final(step, c.write_out);
-    // folded orthonormalisation of the projection form: the even reduction leaves Gram
-    // partials and k_orth_chain (no Gram pass, panel rows over several workgroups) replaces
-    // k_orth_chol
-    const bool qf = p->qfold(step, c.write_out);
-    const bool xg = c.xgram && it == 1 && !even;  // the exchange left the summed Q's Gram
-    float* ss = p->dev<float>(p->o_ss);
+namespace {
 
-    if ((qf && proj) || xg) {
+// ------------------------------------------------- fp32 / bf16 plans up to rank 32 ------
+// One helper per stage of an iteration; each fills one argument struct from the route
+// (psgd_plan.h, IterRoute) and launches. None of them re-derives a flag.
+struct Iter {
+    psgd_plan* p;
+    int64_t step;
+    int it;
+    IterRoute r;
+    psgd_plan::Span sp;
+    hipStream_t s;
+    const StepCtx& c;
+    float* in() const { return r.even ? p->P : p->Q; }
+    float* out() const { return r.even ? p->Q : p->P; }
+    // where the previous iteration's reduction left the per-item sums of squares of its
+    // out-factor (this iteration's raw in-factor)
+    const float* prev_ss() const { return p->dev<float>(p->o_ss) + size_t((it - 1) & 1) * p->ss_stride; }
+};
+
+int orth_stage(const Iter& i) {
+    psgd_plan* p = i.p;
+    if (i.r.orth == IterRoute::OrthChain) {
         ChainArgs ca{};
-        ca.units = p->dev(p->units_q) + sp.uq[0];
-        ca.uitems = p->dev(p->uitems) + 2 * sp.uq[0];
+        ca.units = p->dev(p->units_q) + i.sp.uq[0];
+        ca.uitems = p->dev(p->uitems) + 2 * i.sp.uq[0];
         ca.gram = p->dev<double>(p->o_gram);
         // the even iteration's reduced Q: k_reduce's yloc (world size 1) or the exchange's
         // summed copy (history slot 2, psgd_aggregate_ipc)
-        ca.raw = xg ? p->hist(2, it - 1) : p->hist(1, it - 1);
-        ca.state = in;
-        ca.hx = p->hist(0, it);
+        ca.raw = p->hist(i.r.chain_from_exchange ? 2 : 1, i.it - 1);
+        ca.state = i.in();
+        ca.hx = p->hist(0, i.it);
         ca.rfac = p->dev<float>(p->o_rq);
-        PSGD_HIP(launch_orth_chain(ca, sp.uq[1] - sp.uq[0], p->panel_q, p->rbucket, s));
-    } else if (!fused && !fused0) {
+        PSGD_HIP(launch_orth_chain(ca, i.sp.uq[1] - i.sp.uq[0], p->panel_q, p->rbucket, i.s));
+    } else if (i.r.orth == IterRoute::OrthLaunch) {
         OrthArgs oa{};
-        const int32_t* ur = even ? sp.up : sp.uq;
-        oa.units = p->dev(even ? p->units_p : p->units_q) + ur[0];
-        oa.state = in;
-        oa.hx = p->hist(0, it);
-        oa.save = it > 0 ? p->hist(2, it - 1) : nullptr;  // keep the all-reduced factor of it-1
-        oa.rfac = proj ? p->dev<float>(p->o_rq) : nullptr;
+        const int32_t* ur = i.r.even ? i.sp.up : i.sp.uq;
+        oa.units = p->dev(i.r.even ? p->units_p : p->units_q) + ur[0];
+        oa.state = i.in();
+        oa.hx = p->hist(0, i.it);
+        oa.save = i.it > 0 ? p->hist(2, i.it - 1) : nullptr;  // keep the all-reduced factor of it-1
+        oa.rfac = i.r.proj ? p->dev<float>(p->o_rq) : nullptr;
         const int nunits = ur[1] - ur[0];
-        if (nunits > 0) PSGD_HIP(launch_orth(oa, nunits, p->rbucket, even ? p->panel_p : p->panel_q, p->orth_chol, s));
+        if (nunits > 0)
+            PSGD_HIP(launch_orth(oa, nunits, p->rbucket, i.r.even ? p->panel_p : p->panel_q, p->orth_chol, i.s));
     }
+    return PSGD_OK;
+}
 
-    // where the previous iteration's reduction left the per-item sums of squares of its
-    // out-factor (this iteration's raw in-factor) and the per-group item ranges (after an
-    // odd-even pass the previous even reduction ran over its own item list)
-    const float* prev_ss = ss + size_t((it - 1) & 1) * p->ss_stride;
-    const bool oe_prev2 = !even && it >= 2 && p->oe_at(step, it - 2, c.write_out) && p->fused_norm(c.fuse, it - 2);
-    const int32_t* prev_grng = p->dev(even ? p->grng_odd : oe_prev2 ? p->grng_oe_items : p->grng_even);
-    // odd-even pass: this odd iteration and the next (even) one's product in one gradient pass
-    // (k_final_oe); its P rows need no reduction, the even iteration reduces its partials
-    if (fused && c.span == nullptr && p->oe_at(step, it, c.write_out)) {
-        FinalArgs fa{};
-        fa.mats = p->dev(p->mats);
-        fa.tiles = p->dev(p->tiles_oe);
-        const int nfin = int(p->tiles_oe.size());
-        fa.grads = p->grad_tab.table();
-        fa.x = p->hist(c.raw_slot, it - 1);
-        fill_terms(p, step, it, fa.res);
-        fa.nres = it;
-        fa.yloc = p->hist(1, it);
-        fa.state = out;
-        fa.ss_in = prev_ss;
-        fa.rng = p->dev(p->rng_oe);
-        fa.rsel = oe_prev2 ? 1 : 0;  // (an odd iteration) the even items, or the ones after an odd-even pass
-        fa.xstate = in;
-        fa.hx = p->hist(0, it);
-        fa.ntiles = nfin;
-        fa.oe_part = p->dev<float>(p->o_oe_part);
-        fa.oe_ss = p->dev<float>(p->o_oe_ss);
-        PSGD_HIP(launch_final_oe(p->dtype, it, fin_bucket(p->fin_smax), fa, nfin, s, nullptr));
-        return PSGD_OK;
+// what k_final_oe and the fused last iteration share: the in-factor (raw, with the previous
+// reduction's sums of squares, when the rank-1 norm is folded), the earlier terms, the out-factor
+FinalArgs final_args(const Iter& i) {
+    const psgd_plan* p = i.p;
+    FinalArgs fa{};
+    fa.mats = p->dev(p->mats);
+    fa.grads = p->grad_tab.table();
+    fa.x = i.r.fused ? p->hist(i.c.raw_slot, i.it - 1) : p->hist(0, i.it);
+    fill_terms(p, i.step, i.it, fa.res);
+    fa.nres = i.it;
+    fa.yloc = p->hist(1, i.it);
+    fa.state = i.out();
+    if (i.r.fused) {
+        fa.ss_in = i.prev_ss();  // the in-factor Q came from an even iteration's reduction
+        fa.rsel = i.r.prev_after_oe ? 1 : 0;  // the even items, or the ones after an odd-even pass
+        fa.xstate = i.in();
+        fa.hx = p->hist(0, i.it);
     }
-    const bool oe_prev = even && it >= 1 && c.span == nullptr && p->oe_at(step, it - 1, c.write_out) &&
-                         p->fused_norm(c.fuse, it - 1);
-    if (it == p->iters - 1 && p->fused_final(step, c.write_out)) {
-        // last iteration, odd: product + residual (+ output at world size 1) in one pass
-        FinalArgs fa{};
-        fa.out_nt = p->out_nt;
-        fa.mats = p->dev(p->mats);
-        // the K-term form on its own row blocks when the plan has them (MatDesc::fin_rows_kt)
-        const bool own_kt = !proj && !p->tiles_fin_kt.empty();
-        const int32_t(&fr)[2] = own_kt ? sp.fin_kt : sp.fin;
-        fa.tiles = p->dev(own_kt ? p->tiles_fin_kt : p->tiles_fin) + fr[0];
-        fa.grads = p->grad_tab.table();
-        fa.out = c.out;
-        fa.x = fused ? p->hist(c.raw_slot, it - 1) : p->hist(0, it);
-        fill_terms(p, step, it, fa.res);
-        fa.nres = it;
-        fa.write_out = c.write_out ? 1 : 0;
-        fa.yloc = p->hist(1, it);
-        fa.state = out;
-        fa.xout = c.xout;
-        if (fused) {
-            fa.ss_in = prev_ss;  // the in-factor Q came from an even iteration's reduction
-            fa.rng = p->dev(own_kt ? p->rng_fin_kt : p->rng_fin) + fr[0];
-            fa.rsel = oe_prev2 ? 1 : 0;
-            fa.xstate = in;
-            fa.hx = p->hist(0, it);
-        }
-        const int nfin = fr[1] - fr[0];
-        if (proj) {  // no error-feedback terms: P_0 and R' only (rank 1: P_0 and the matrix's c)
-            fa.proj_p0 = p->hist(0, 0);
-            fa.proj_r = p->dev<float>(p->o_rq);
-            fill_terms(p, step, 0, fa.res);
-            fa.nres = kFinProj;
-        }
-        fa.ntiles = nfin;
-        if (c.fl && c.write_out) fa.flat = *c.fl;  // uncompressed tensors ride in the same launch
-        if (nfin + fa.flat.nitems == 0) return PSGD_OK;
-        std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
-        if (int st = timing_begin(p, s, &ev, true)) return st;  // benchmark timing: the final pass
-        TimedScope ts(ev);
-        if (c.mix)  // psgd_aggregate_mixed: bf16 output, and the ingest fold of the single-pass form
-            PSGD_HIP(launch_final_mix(p->rbucket, fa.nres, fin_bucket(p->fin_smax), c.mix_in && it == 0, fa, *c.mix, nfin,
-                                      s, nullptr));
-        else
-            PSGD_HIP(launch_final_odd(p->dtype, p->rbucket, fa.nres, fin_bucket(p->fin_smax), fa, nfin, s));
-        return PSGD_OK;
-    }
+    return fa;
+}
 
+// odd-even pass: this odd iteration and the next (even) one's product in one gradient pass
+// (k_final_oe); its P rows need no reduction, the even iteration reduces its partials
+int odd_even_stage(const Iter& i) {
+    const psgd_plan* p = i.p;
+    FinalArgs fa = final_args(i);
+    fa.tiles = p->dev(p->tiles_oe);
+    fa.rng = p->dev(p->rng_oe);
+    fa.ntiles = int32_t(p->tiles_oe.size());
+    fa.oe_part = p->dev<float>(p->o_oe_part);
+    fa.oe_ss = p->dev<float>(p->o_oe_ss);
+    PSGD_HIP(launch_final_oe(p->dtype, i.it, fin_bucket(p->fin_smax), fa, fa.ntiles, i.s, nullptr));
+    return PSGD_OK;
+}
+
+// last iteration, odd: product + residual (+ output at world size 1) in one pass
+int final_stage(const Iter& i) {
+    psgd_plan* p = i.p;
+    const StepCtx& c = i.c;
+    FinalArgs fa = final_args(i);
+    fa.out_nt = p->out_nt;
+    // the K-term form on its own row blocks when the plan has them (MatDesc::fin_rows_kt)
+    const int32_t(&fr)[2] = i.r.own_kt ? i.sp.fin_kt : i.sp.fin;
+    fa.tiles = p->dev(i.r.own_kt ? p->tiles_fin_kt : p->tiles_fin) + fr[0];
+    if (i.r.fused) fa.rng = p->dev(i.r.own_kt ? p->rng_fin_kt : p->rng_fin) + fr[0];
+    fa.out = c.out;
+    fa.write_out = c.write_out ? 1 : 0;
+    fa.xout = c.xout;
+    if (i.r.proj) {  // no error-feedback terms: P_0 and R' only (rank 1: P_0 and the matrix's c)
+        fa.proj_p0 = p->hist(0, 0);
+        fa.proj_r = p->dev<float>(p->o_rq);
+        fill_terms(p, i.step, 0, fa.res);
+    }
+    fa.nres = i.r.final_nres;
+    fa.ntiles = fr[1] - fr[0];
+    if (c.fl && c.write_out) fa.flat = *c.fl;  // uncompressed tensors ride in the same launch
+    if (fa.ntiles + fa.flat.nitems == 0) return PSGD_OK;
+    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    if (int st = timing_begin(p, i.s, &ev, true)) return st;  // benchmark timing: the final pass
+    TimedScope ts(ev);
+    PSGD_HIP(launch_final_pass(p, i.r, fa, c.mix, fa.ntiles, i.s, nullptr));
+    return PSGD_OK;
+}
+
+// the fixed-order reduction of the product's partials into the out-factor; with the rank-1 norm
+// folded it also normalises the in-factor (its items follow the main ones)
+int reduce_stage(const Iter& i, const ProductArgs& pa) {
+    psgd_plan* p = i.p;
+    const StepCtx& c = i.c;
+    const IterRoute& r = i.r;
+    const psgd_plan::Span& sp = i.sp;
+    const bool from_oe = r.pass == IterRoute::PassFromOddEven;
+    ReduceArgs ra{};
+    ra.mats = pa.mats;
+    const int32_t* rr = r.even ? sp.re : sp.ro;  // this parity's items (out-factor side)
+    const int32_t* rn = r.even ? sp.ro : sp.re;  // the other parity's items (in-factor side)
+    ra.items = p->dev(r.even ? p->red_even : p->red_odd) + rr[0];
+    ra.part = pa.part;
+    ra.yloc = p->hist(1, i.it);
+    ra.state = i.out();
+    ra.even = r.even ? 1 : 0;
+    ra.nmain = rr[1] - rr[0];
+    if (from_oe) {  // the odd-even pass's block partials, per matrix [blocks][m]
+        ra.items = p->dev(p->red_oe);
+        ra.part = p->dev<float>(p->o_oe_part);
+        ra.nmain = int32_t(p->red_oe.size());
+    }
+    if (r.fused0) {  // normalise the state P in place + history copy (P-side items)
+        ra.ss_in = pa.ss0;
+        ra.grng_in = p->dev(p->grng_ss0);
+        ra.nitems = p->dev(p->red_odd) + sp.ro[0];
+        ra.nnorm = sp.ro[1] - sp.ro[0];
+        ra.raw = i.in();
+    }
+    if (r.fused) {  // in-factor items: the other parity's item list; after an odd-even pass the
+                    // blocks' sums of P^2, and the previous even reduction ran over red_oe
+        ra.ss_in = from_oe ? p->dev<float>(p->o_oe_ss) : i.prev_ss();
+        ra.grng_in = p->dev(from_oe ? p->grng_oe : r.even ? p->grng_odd : r.prev_after_oe ? p->grng_oe_items : p->grng_even);
+        ra.nitems = p->dev(r.even ? p->red_odd : p->red_even) + rn[0];
+        ra.nnorm = rn[1] - rn[0];
+        ra.raw = p->hist(c.raw_slot, i.it - 1);
+    }
+    if (r.fused || r.fused0) {
+        ra.xstate = i.in();
+        ra.hx = p->hist(0, i.it);
+    }
+    // ss_out is indexed by the launch's block (item) index: offset like the item list
+    if (r.ss_out) ra.ss_out = p->dev<float>(p->o_ss) + size_t(i.it & 1) * p->ss_stride + rr[0];
+    ra.xout = c.xout;
+    if (r.gram_out) {  // the Q panels' Gram for k_orth_chain
+        ra.gram = p->dev<double>(p->o_gram) + size_t(rr[0]) * kGramStride;
+        ra.gram_r = p->rbucket;
+    }
+    if (ra.nmain + ra.nnorm > 0) PSGD_HIP(launch_reduce(ra, ra.nmain + ra.nnorm, i.s));
+    return PSGD_OK;
+}
+
+
+// the product of PassEven / PassOdd (PassFromOddEven: accumulated by the odd-even pass, no
+// launch), then its reduction
+int product_stage(const Iter& i) {
+    psgd_plan* p = i.p;
+    const StepCtx& c = i.c;
+    const IterRoute& r = i.r;
+    const psgd_plan::Span& sp = i.sp;
     ProductArgs pa{};
     pa.mats = p->dev(p->mats);
     pa.grads = p->grad_tab.table();
-    pa.x = fused ? p->hist(c.raw_slot, it - 1) : fused0 ? in : p->hist(0, it);  // fused: the raw factor
+    pa.x = r.fused ? p->hist(c.raw_slot, i.it - 1) : r.fused0 ? i.in() : p->hist(0, i.it);  // fused: the raw factor
     pa.part = p->dev<float>(p->o_part);
-    if (fused0) pa.ss0 = p->dev<float>(p->o_ss0);
-    fill_terms(p, step, it, pa.res);
-    pa.nres = it;
-    if (oe_prev) {
-        // the product of this even iteration was accumulated by the odd-even pass
-    } else if (even) {
+    if (r.fused0) pa.ss0 = p->dev<float>(p->o_ss0);
+    fill_terms(p, i.step, i.it, pa.res);
+    pa.nres = i.it;
+    if (r.pass == IterRoute::PassEven) {
         // persistent k_even: this span's workgroups [wg[0], wg[1]) of the segmentation
         pa.segs = p->dev(p->segs);
         pa.wg_seg = p->dev(p->wg_seg) + sp.wg[0];
         pa.nwg = sp.wg[1] - sp.wg[0];
         // world size > 1 (no output written here): the first iteration's launch also packs the
         // uncompressed tensors, ahead of every collective
-        if (c.fl && !c.write_out && it == 0) pa.flat = *c.fl;
+        if (c.fl && !c.write_out && i.it == 0) pa.flat = *c.fl;
         if (int st = even_stamps_begin(p, pa)) return st;
-        PSGD_HIP(launch_even(p->dtype, p->rbucket, it, pa, pa.nwg, s));
-        if (int st = even_stamps_end(p, pa, s)) return st;
-    } else {
+        PSGD_HIP(launch_even(p->dtype, p->rbucket, i.it, pa, pa.nwg, i.s));
+        if (int st = even_stamps_end(p, pa, i.s)) return st;
+    } else if (r.pass == IterRoute::PassOdd) {
         if (sp.ov[1] > sp.ov[0]) {
             pa.tiles = p->dev(p->tiles_ov) + sp.ov[0];
-            PSGD_HIP(launch_product_odd(p->dtype, p->rbucket, it, pa, sp.ov[1] - sp.ov[0], s));
+            PSGD_HIP(launch_product_odd(p->dtype, p->rbucket, i.it, pa, sp.ov[1] - sp.ov[0], i.s));
         }
         if (sp.om[1] > sp.om[0]) {
             pa.tiles = p->dev(p->tiles_om) + sp.om[0];
-            PSGD_HIP(launch_odd_mfma(p->dtype, p->rbucket, it, pa, sp.om[1] - sp.om[0], s));
+            PSGD_HIP(launch_odd_mfma(p->dtype, p->rbucket, i.it, pa, sp.om[1] - sp.om[0], i.s));
         }
     }
+    return reduce_stage(i, pa);
+}
+}  // namespace
 
-    ReduceArgs ra{};
-    ra.mats = pa.mats;
-    const int32_t* rr = even ? sp.re : sp.ro;  // this parity's items (out-factor side)
-    const int32_t* rn = even ? sp.ro : sp.re;  // the other parity's items (in-factor side)
-    ra.items = p->dev(even ? p->red_even : p->red_odd) + rr[0];
-    ra.part = pa.part;
-    ra.yloc = p->hist(1, it);
-    ra.state = out;
-    ra.even = even ? 1 : 0;
-    ra.nmain = rr[1] - rr[0];
-    if (oe_prev) {  // the odd-even pass's block partials, per matrix [blocks][m]
-        ra.items = p->dev(p->red_oe);
-        ra.part = p->dev<float>(p->o_oe_part);
-        ra.nmain = int32_t(p->red_oe.size());
-    }
-    if (fused0) {  // normalise the state P in place + history copy (P-side items)
-        ra.ss_in = pa.ss0;
-        ra.grng_in = p->dev(p->grng_ss0);
-        ra.nitems = p->dev(p->red_odd) + sp.ro[0];
-        ra.nnorm = sp.ro[1] - sp.ro[0];
-        ra.raw = in;
-        ra.xstate = in;
-        ra.hx = p->hist(0, it);
-    }
-    if (fused) {  // in-factor items: the other parity's item list (in-factor side)
-        ra.ss_in = oe_prev ? p->dev<float>(p->o_oe_ss) : prev_ss;  // odd-even: the blocks' sums of P^2
-        ra.grng_in = oe_prev ? p->dev(p->grng_oe) : prev_grng;
-        ra.nitems = p->dev(even ? p->red_odd : p->red_even) + rn[0];
-        ra.nnorm = rn[1] - rn[0];
-        ra.raw = p->hist(c.raw_slot, it - 1);
-        ra.xstate = in;
-        ra.hx = p->hist(0, it);
-    }
-    // ss_out is indexed by the launch's block (item) index: offset like the item list
-    if (p->fused_norm(c.fuse, it + 1) && it + 1 < p->iters) ra.ss_out = ss + size_t(it & 1) * p->ss_stride + rr[0];
-    ra.xout = c.xout;
-    if (qf && even && it + 2 == p->iters) {  // the Q panels' Gram for k_orth_chain
-        ra.gram = p->dev<double>(p->o_gram) + size_t(rr[0]) * kGramStride;
-        ra.gram_r = p->rbucket;
-    }
-    if (ra.nmain + ra.nnorm > 0) PSGD_HIP(launch_reduce(ra, ra.nmain + ra.nnorm, s));
-    return PSGD_OK;
+hipError_t psgd::launch_final_pass(const psgd_plan* p, const IterRoute& r, const FinalArgs& a, const MixArgs* mix,
+                                   int ntiles, hipStream_t s, int* waves) {
+    const int smax = fin_bucket(p->fin_smax);
+    if (smax == 0) return hipErrorInvalidValue;  // no instance serves rows of that many segments
+    if (mix)  // psgd_aggregate_mixed: bf16 output, and the ingest fold of the single-pass form
+        return launch_final_mix(p->rbucket, r.final_nres, smax, r.ingest, a, *mix, ntiles, s, waves);
+    return launch_final_odd(p->dtype, p->rbucket, r.final_nres, smax, a, ntiles, s, waves);
 }
 
+hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArgs& a, const MixArgs* mix, int ntiles,
+                                 hipStream_t s, int* waves) {
+    a.out_nt = o.out_nt;
+    const int R = p->rbucket, I = p->iters;
+    if (o.kind == OutRoute::Lowrank)
+        return mix ? launch_lowrank_mix(R, I, a, *mix, ntiles, s, waves) : launch_lowrank_out(p->dtype, R, I, a, ntiles, s);
+    switch (o.inst) {
+        case OutRoute::Mix: return launch_apply_mix(R, I, a, *mix, ntiles, s, waves);
+        case OutRoute::MixW: return launch_apply_mix_w(R, I, a, *mix, ntiles, s, waves);
+        default: return launch_apply(p->dtype, R, I, o.shared, a, ntiles, s);
+    }
+}
+
+int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s, StepCtx c) {
+    if (p->f64()) return compress_f64(p, grads, step, it, s);
+    if (p->wide()) return compress_wide(p, grads, step, it, s);
+    if (int st = refresh_pointers(p, grads, s)) return st;
+    const Iter i{p, step, it, p->route(step, it, c), c.span ? *c.span : p->full_span(), s, c};
+    if (int st = orth_stage(i)) return st;
+    switch (i.r.pass) {
+        case IterRoute::PassOddEven: return odd_even_stage(i);
+        case IterRoute::PassFinal: return final_stage(i);
+        default: return product_stage(i);
+    }
+}
+
+// World-size-1 step (psgd_aggregate / psgd_aggregate_flat / psgd_aggregate_mixed): the rank-1 joint
+// norm folded, the output written by the fused last iteration where the plan has one
 int psgd::aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c) {
-    c.fuse = c.write_out = true;
+    c = world1_ctx(c);
     for (int it = 0; it < p->iters; ++it)
         if (int st = compress_impl(p, grads, step, it, s, c)) return st;
-    if (p->fused_final(step, true)) return PSGD_OK;  // output written by the fused last iteration
     return decompress_impl(p, grads, c.out, step, 1, s, c);
 }
 
@@ -512,6 +549,8 @@ int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t s
                           StepCtx c) {
     if (p->f64()) return decompress_f64(p, grads, out, step, world, s);
     if (p->wide()) return decompress_wide(p, grads, out, step, world, s);
+    const OutRoute o = p->out_route(step, world, c);
+    if (o.kind == OutRoute::None) return PSGD_OK;  // output written by the fused last iteration
     if (int st = refresh_pointers(p, grads, s)) return st;
     const psgd_plan::Span sp = c.span ? *c.span : p->full_span();
     const int nt = sp.tiles[1] - sp.tiles[0];
@@ -523,40 +562,18 @@ int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t s
     aa.out = out;
     fill_terms(p, step, I, aa.res);
     float* last = p->even(step, I - 1) ? p->Q : p->P;  // all-reduced factor of the last iteration
-    for (int k = 0; k < kMaxTerms; ++k) aa.apx.p[k] = aa.apx.q[k] = nullptr;
-    for (int k = 0; k < I; ++k) {
-        const bool e = p->even(step, k);
-        // fused (world 1): the reduced factor was never copied to hist(2): use hist(1)
-        float* ybar = k + 1 < I ? p->hist(p->fused_norm(c.fuse, k + 1) ? 1 : 2, k) : last;
-        aa.apx.p[k] = e ? p->hist(0, k) : ybar;
-        aa.apx.q[k] = e ? ybar : p->hist(0, k);
-    }
+    fill_terms(p, step, I, aa.apx, [&](int k) { return p->hist(0, k); },
+               [&](int k) { return k + 1 < I ? p->hist(o.reduced_slot, k) : last; });
     aa.nterms = I;
     aa.alpha = float(1.0 / double(world));  // reference alpha = 1 / num_workers (:218)
-    aa.out_nt = world == 1 ? p->out_nt : 0;
-    if (p->fused_final(step, false)) {
-        // the residual was written by the fused last iteration: output only
-        aa.ntiles = nt;
-        if (c.mix) {  // psgd_aggregate_mixed_comm: bf16 output, the flat tail's round items first
-            if (c.fl) aa.flat = *c.fl;
-            if (nt + aa.flat.nitems > 0) PSGD_HIP(launch_lowrank_mix(p->rbucket, I, aa, *c.mix, nt, s, nullptr));
-            return PSGD_OK;
-        }
-        if (nt > 0) PSGD_HIP(launch_lowrank_out(p->dtype, p->rbucket, I, aa, nt, s));
-        return PSGD_OK;
-    }
     aa.ntiles = nt;
-    if (c.fl) aa.flat = *c.fl;  // uncompressed tensors ride in the same launch
+    if (c.fl && o.flat) aa.flat = *c.fl;  // uncompressed tensors (mixed_comm: their round items) ride in the launch
     if (nt + aa.flat.nitems == 0) return PSGD_OK;
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
-    if (int st = timing_begin(p, s, &ev, true)) return st;
+    if (o.timed)
+        if (int st = timing_begin(p, s, &ev, true)) return st;
     TimedScope ts(ev);
-    if (c.mix && world == 1)  // psgd_aggregate_mixed (world size 1): bf16 output
-        PSGD_HIP(launch_apply_mix(p->rbucket, I, aa, *c.mix, nt, s, nullptr));
-    else if (c.mix)  // psgd_aggregate_mixed_comm at W > 1: two term sets, bf16 output
-        PSGD_HIP(launch_apply_mix_w(p->rbucket, I, aa, *c.mix, nt, s, nullptr));
-    else
-        PSGD_HIP(launch_apply(p->dtype, p->rbucket, I, world == 1, aa, nt, s));
+    PSGD_HIP(launch_out_pass(p, o, aa, c.mix, nt, s, nullptr));
     return PSGD_OK;
 }
 
@@ -573,15 +590,6 @@ int bucket_span(const psgd_plan* p, int32_t b, psgd_plan::Span* sp) {
     if (b < 0 || b >= int32_t(p->spans.size())) return fail(PSGD_ERR_VALUE, "bucket out of range");
     *sp = p->spans[b];
     return PSGD_OK;
-}
-
-// World-size-1 step (psgd_aggregate / psgd_aggregate_flat): the rank-1 joint norm folded, the
-// output written by the fused last iteration where the plan has one
-int aggregate_impl(psgd_plan* p, void* const* grads, void* out, int64_t step, hipStream_t s, const FlatArgs* fl) {
-    StepCtx c;
-    c.fl = fl;
-    c.out = out;
-    return aggregate_ctx(p, grads, step, s, c);
 }
 
 int check_terms(int32_t nterms, const float* const* a, const float* const* b) {
@@ -634,51 +642,39 @@ int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_
                                     last && has_flat ? tail : nullptr, last && has_flat ? size_t(f->total) : 0, s))
             return st;
     }
-    if (!mix) return decompress_impl(p, grads, out, step, world, s, StepCtx{});
+    StepCtx d = comm_out_ctx(mix);
+    if (!mix) return decompress_impl(p, grads, out, step, world, s, d);
     // the round items ride in every final launch built for them; a 1-rank communicator's unfused
     // final pass is the world-size-1 instance, whose flat items ingest: the round follows it
-    const bool ride = world > 1 || p->fused_final(step, false);
-    StepCtx d;
-    d.mix = mix;
+    const OutRoute o = p->out_route(step, world, d);
+    const bool ride = o.kind == OutRoute::Lowrank || o.inst == OutRoute::MixW;
     d.fl = has_flat && ride ? &fa : nullptr;
     if (int st = decompress_impl(p, grads, out, step, world, s, d)) return st;
     if (has_flat && !ride) PSGD_HIP(launch_flat_round(fa, *mix, s));
     return PSGD_OK;
 }
 
-namespace {
-
-int aggregate_comm_body(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f,
-                        void* const* unc, void* flat_out, psgd_comm* comm, hipStream_t s) {
-    return aggregate_comm_ctx(p, grads, out, step, f, unc, flat_out, comm, s, nullptr);
-}
-
-}  // namespace
-
 extern "C" {
 
 int psgd_compress(psgd_plan* p, void* const* grads, int64_t step, int32_t it, void* stream) {
-    if (!p || !grads) return fail(PSGD_ERR_VALUE, "null argument");
-    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (step < 0 || it < 0 || it >= p->iters) return fail(PSGD_ERR_VALUE, "step/iteration out of range");
+    if (int st = check_call(p && grads, p && p->bound, p && step >= 0 && it >= 0 && it < p->iters, "step/iteration out of range"))
+        return st;
     DevScope scope(p->device);
     return compress_impl(p, grads, step, it, static_cast<hipStream_t>(stream), StepCtx{});
 }
 
 int psgd_decompress(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world,
                     void* stream) {
-    if (!p || !grads || !out) return fail(PSGD_ERR_VALUE, "null argument");
-    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (step < 0 || world < 1) return fail(PSGD_ERR_VALUE, "step/world size out of range");
-    if (reinterpret_cast<uintptr_t>(out) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    if (int st = check_call(p && grads && out, p && p->bound, step >= 0 && world >= 1, "step/world size out of range"))
+        return st;
+    if (int st = check_out(out)) return st;
     DevScope scope(p->device);
     return decompress_impl(p, grads, out, step, world, static_cast<hipStream_t>(stream), StepCtx{});
 }
 
 int psgd_compress_bucket(psgd_plan* p, void* const* grads, int64_t step, int32_t it, int32_t bucket, void* stream) {
-    if (!p || !grads) return fail(PSGD_ERR_VALUE, "null argument");
-    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (step < 0 || it < 0 || it >= p->iters) return fail(PSGD_ERR_VALUE, "step/iteration out of range");
+    if (int st = check_call(p && grads, p && p->bound, p && step >= 0 && it >= 0 && it < p->iters, "step/iteration out of range"))
+        return st;
     psgd_plan::Span sp;
     if (int st = bucket_span(p, bucket, &sp)) return st;
     DevScope scope(p->device);
@@ -689,10 +685,9 @@ int psgd_compress_bucket(psgd_plan* p, void* const* grads, int64_t step, int32_t
 
 int psgd_decompress_bucket(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, int32_t bucket,
                            void* stream) {
-    if (!p || !grads || !out) return fail(PSGD_ERR_VALUE, "null argument");
-    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (step < 0 || world < 1) return fail(PSGD_ERR_VALUE, "step/world size out of range");
-    if (reinterpret_cast<uintptr_t>(out) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    if (int st = check_call(p && grads && out, p && p->bound, step >= 0 && world >= 1, "step/world size out of range"))
+        return st;
+    if (int st = check_out(out)) return st;
     psgd_plan::Span sp;
     if (int st = bucket_span(p, bucket, &sp)) return st;
     DevScope scope(p->device);
@@ -704,21 +699,20 @@ int psgd_decompress_bucket(psgd_plan* p, void* const* grads, void* out, int64_t 
 // World size 1: the pointer tables are selected (or uploaded) on the caller's stream, then the
 // step's launches follow on it.
 int psgd_aggregate(psgd_plan* p, void* const* grads, void* out, int64_t step, void* stream) {
-    if (!p || !grads || !out) return fail(PSGD_ERR_VALUE, "null argument");
-    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
-    if (reinterpret_cast<uintptr_t>(out) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    if (int st = check_call(p && grads && out, p && p->bound, step >= 0, "step out of range")) return st;
+    if (int st = check_out(out)) return st;
     DevScope scope(p->device);
-    return aggregate_impl(p, grads, out, step, static_cast<hipStream_t>(stream), nullptr);
+    StepCtx c;
+    c.out = out;
+    return aggregate_ctx(p, grads, step, static_cast<hipStream_t>(stream), c);
 }
 
 int psgd_aggregate_flat(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f,
                         void* const* unc, void* flat_out, void* stream) {
     if (!f || f->total == 0) return psgd_aggregate(p, grads, out, step, stream);
-    if (!p || !grads || !out || !unc || !flat_out) return fail(PSGD_ERR_VALUE, "null argument");
-    if (!p->bound || !f->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
-    if (reinterpret_cast<uintptr_t>(out) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    if (int st = check_call(p && grads && out && unc && flat_out, p && p->bound && f->bound, step >= 0, "step out of range"))
+        return st;
+    if (int st = check_out(out)) return st;
     if (f->dtype != p->dtype || f->device != p->device || p->f64() || p->wide()) {  // separate launches
         if (int st = psgd_aggregate(p, grads, out, step, stream)) return st;
         return psgd_flat_pack(f, unc, flat_out, 1, stream);
@@ -727,7 +721,10 @@ int psgd_aggregate_flat(psgd_plan* p, void* const* grads, void* out, int64_t ste
     hipStream_t s = static_cast<hipStream_t>(stream);
     FlatArgs a;
     if (int st = flat_args(f, unc, flat_out, 1, s, &a)) return st;
-    return aggregate_impl(p, grads, out, step, s, &a);
+    StepCtx c;
+    c.fl = &a;
+    c.out = out;
+    return aggregate_ctx(p, grads, step, s, c);
 }
 
 // World size W in one call (include/psgd.h): per iteration the kernels, then the in-place SUM
@@ -736,25 +733,22 @@ int psgd_aggregate_flat(psgd_plan* p, void* const* grads, void* out, int64_t ste
 // blocks psgd_compress / all_reduce / psgd_decompress (reference powersgd.py:172-230).
 int psgd_aggregate_comm(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
                         void* flat_out, psgd_comm* comm, void* stream) {
-    if (!p || !grads || !out || !comm) return fail(PSGD_ERR_VALUE, "null argument");
-    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
+    if (int st = check_call(p && grads && out && comm, p && p->bound, step >= 0, "step out of range")) return st;
     if (p->f64()) return fail(PSGD_ERR_DTYPE, "psgd_aggregate_comm takes fp32/bf16 plans (fp32 factors)");
-    if (reinterpret_cast<uintptr_t>(out) % 16) return fail(PSGD_ERR_LAYOUT, "output buffer must be 16-byte aligned");
+    if (int st = check_out(out)) return st;
     const bool has_flat = f && f->total > 0;
-    if (has_flat) {
-        if (!unc || !flat_out) return fail(PSGD_ERR_VALUE, "null argument");
-        if (!f->bound) return fail(PSGD_ERR_STATE, "flat plan is not bound");
-        if (f->dtype != PSGD_F32) return fail(PSGD_ERR_DTYPE, "psgd_aggregate_comm packs fp32 uncompressed tensors");
-    }
+    if (has_flat)
+        if (int st = check_flat(f, unc && flat_out, f->dtype == PSGD_F32, PSGD_ERR_DTYPE,
+                                "psgd_aggregate_comm packs fp32 uncompressed tensors"))
+            return st;
     // a poisoned communicator is refused before the step launches anything: the caller's
     // gradients and the P/Q state stay as they were
     std::string why;
     if (comm_poisoned(comm, &why))
         return fail(PSGD_ERR_STATE, ("communicator unusable after an earlier failure: " + why).c_str());
     DevScope scope(p->device);
-    const int st = aggregate_comm_body(p, grads, out, step, has_flat ? f : nullptr, unc, flat_out, comm,
-                                       static_cast<hipStream_t>(stream));
+    const int st = aggregate_comm_ctx(p, grads, out, step, has_flat ? f : nullptr, unc, flat_out, comm,
+                                      static_cast<hipStream_t>(stream), nullptr);
     // a failure past the argument checks can leave this rank's collective sequence short of its
     // peers': the communicator refuses every later call (psgd_comm.cpp, comm_poison)
     if (st) comm_poison(comm, psgd_last_error());

@@ -1474,66 +1474,59 @@ hipError_t resident_waves(F fn, int NT, int* waves) {
     return hipSuccess;
 }
 
+// Factor terms k_apply and its mixed forms cache in registers (NI; -1: loaded per use): up to 4 at
+// ranks <= 8 when the term sets are shared (world size 1); with two term sets (local and
+// all-reduced) 4 / 3 / 2 at ranks <= 2 / 4 / 8: the 4-term rank-4 and rank-8 instances spilled
+// VGPRs to scratch (tools/regs.py), the per-use loads do not. Ranks 16 / 32 take the matrix-core
+// tiles (apply_tile_mfma, any term count), whose fallback loads factor rows per element. The mixed
+// forms are bit for bit their three-stage definition because they run the same NI.
+constexpr int apply_ni(int R, int nterms, bool shared) {
+    if (R >= 16) return -1;
+    const int maxni = shared || R <= 2 ? 4 : R == 4 ? 3 : 2;
+    return nterms >= 1 && nterms <= maxni ? nterms : -1;
+}
+
+// Calls f(std::integral_constant<int, N>) for the N of the instantiated set NS... that equals the
+// run-time ni, else for N = -1 (NS is the kernel's set of register-cached instances)
+template <int... NS, typename F>
+hipError_t by_ni(int ni, F f) {
+    hipError_t e = hipSuccess;
+    const bool hit = ((ni == NS && (e = f(std::integral_constant<int, NS>{}), true)) || ...);
+    return hit ? e : f(std::integral_constant<int, -1>{});
+}
+
+// `waves` (if non-null) receives the resident waves per SIMD of the instance that would run;
+// no tiles and no flat items: no launch
 template <int R>
 hipError_t dispatch_apply_mix_r(int nterms, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s,
                                 int* waves) {
-    const dim3 grid(ntiles + a.flat.nitems), block(kBlock);
-    const int NI = nterms <= 4 ? nterms : -1;  // register-cached factor terms, as dispatch_apply_r
-#define PSGD_AM(NN)                                                                                     \
-    do {                                                                                                \
-        if (waves) {                                                                                    \
-            const hipError_t e = a.out_nt ? resident_waves(&k_apply_mix<R, NN, true>, kBlock, waves)   \
-                                          : resident_waves(&k_apply_mix<R, NN, false>, kBlock, waves); \
-            if (e != hipSuccess) return e;                                                              \
-        }                                                                                               \
-        if (ntiles + a.flat.nitems == 0) return hipSuccess;                                             \
-        if (a.out_nt)                                                                                   \
-            timed_launch(&k_apply_mix<R, NN, true>, grid, block, s, a, x);                              \
-        else                                                                                            \
-            timed_launch(&k_apply_mix<R, NN, false>, grid, block, s, a, x);                             \
-    } while (0)
-    switch (NI) {
-        case 1: PSGD_AM(1); break;
-        case 2: PSGD_AM(2); break;
-        case 3: PSGD_AM(3); break;
-        case 4: PSGD_AM(4); break;
-        default: PSGD_AM(-1); break;
-    }
-#undef PSGD_AM
-    return hipGetLastError();
+    auto go = [&](auto N, auto ONT) -> hipError_t {
+        const auto fn = &k_apply_mix<R, decltype(N)::value, decltype(ONT)::value>;
+        if (waves)
+            if (const hipError_t e = resident_waves(fn, kBlock, waves); e != hipSuccess) return e;
+        if (ntiles + a.flat.nitems == 0) return hipSuccess;
+        timed_launch(fn, dim3(ntiles + a.flat.nitems), dim3(kBlock), s, a, x);
+        return hipGetLastError();
+    };
+    return by_ni<1, 2, 3, 4>(apply_ni(R, nterms, true), [&](auto N) {
+        return a.out_nt ? go(N, std::true_type{}) : go(N, std::false_type{});
+    });
 }
 
-// W > 1: the instance k_apply's dispatch picks for two term sets (dispatch_apply_r, !shared: rank 4
-// caches up to 3 terms, its 4-term instance spilled), so the mixed pass runs the same NI
+// W > 1: two term sets (k_apply_mix_w<4, 4> is not instantiated: apply_ni never asks for it)
 template <int R>
 hipError_t dispatch_apply_mix_w(int nterms, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s,
                                 int* waves) {
-    const dim3 grid(ntiles + a.flat.nitems), block(kBlock);
-    constexpr int kMaxNI = R <= 2 ? 4 : 3;
-    const int NI = nterms <= kMaxNI ? nterms : -1;
-#define PSGD_AW(NN)                                                                          \
-    do {                                                                                     \
-        if (waves) {                                                                         \
-            const hipError_t e = resident_waves(&k_apply_mix_w<R, NN>, kBlock, waves);      \
-            if (e != hipSuccess) return e;                                                   \
-        }                                                                                    \
-        if (ntiles + a.flat.nitems == 0) return hipSuccess;                                  \
-        timed_launch(&k_apply_mix_w<R, NN>, grid, block, s, a, x);                           \
-    } while (0)
-    switch (NI) {
-        case 1: PSGD_AW(1); break;
-        case 2: PSGD_AW(2); break;
-        case 3: PSGD_AW(3); break;
-        case 4:
-            if constexpr (kMaxNI >= 4) {
-                PSGD_AW(4);
-                break;
-            }
-            [[fallthrough]];
-        default: PSGD_AW(-1); break;
-    }
-#undef PSGD_AW
-    return hipGetLastError();
+    auto go = [&](auto N) -> hipError_t {
+        const auto fn = &k_apply_mix_w<R, decltype(N)::value>;
+        if (waves)
+            if (const hipError_t e = resident_waves(fn, kBlock, waves); e != hipSuccess) return e;
+        if (ntiles + a.flat.nitems == 0) return hipSuccess;
+        timed_launch(fn, dim3(ntiles + a.flat.nitems), dim3(kBlock), s, a, x);
+        return hipGetLastError();
+    };
+    if constexpr (R <= 2) return by_ni<1, 2, 3, 4>(apply_ni(R, nterms, false), go);
+    else return by_ni<1, 2, 3>(apply_ni(R, nterms, false), go);
 }
 
 // ------------------------------------------------------------------ dispatch ------
@@ -1572,36 +1565,18 @@ hipError_t dispatch_odd(int R, int nres, const ProductArgs& a, int ntiles, hipSt
 template <typename T, int R>
 hipError_t dispatch_apply_r(int nterms, bool shared, const ApplyArgs& a, int ntiles, hipStream_t s) {
     const dim3 grid(ntiles + a.flat.nitems), block(kBlock);
-    // register-cached factor terms: up to 4 at ranks <= 8; ranks 16 / 32 take the matrix-core
-    // tiles (apply_tile_mfma, any term count), whose fallback loads factor rows per element
-    constexpr bool kCache = R <= 8;
-    constexpr int kMaxNI = 4;
-    // world size > 1 (two term sets: local and all-reduced) caches fewer: the 4-term rank-4
-    // and rank-8 instances spilled VGPRs to scratch (tools/regs.py), the per-use loads do not
-    const int maxni = shared ? kMaxNI : (R <= 2 ? 4 : R == 4 ? 3 : 2);
-    const int NI = (kCache && nterms <= maxni) ? nterms : -1;
-#define PSGD_A(NN)                                                                       \
-    do {                                                                                 \
-        if (shared && a.out_nt)                                                          \
-            timed_launch(&k_apply<T, R, NN, true, true>, grid, block, s, a);             \
-        else if (shared)                                                                 \
-            timed_launch(&k_apply<T, R, NN, true>, grid, block, s, a);                   \
-        else                                                                             \
-            timed_launch(&k_apply<T, R, NN, false>, grid, block, s, a);                  \
-    } while (0)
-    if constexpr (kCache) {
-        switch (NI) {
-            case 1: PSGD_A(1); break;
-            case 2: PSGD_A(2); break;
-            case 3: PSGD_A(3); break;
-            case 4: PSGD_A(4); break;
-            default: PSGD_A(-1); break;
-        }
-    } else {
-        PSGD_A(-1);
-    }
-#undef PSGD_A
-    return hipGetLastError();
+    auto go = [&](auto N) -> hipError_t {
+        constexpr int NN = decltype(N)::value;
+        if (shared && a.out_nt)
+            timed_launch(&k_apply<T, R, NN, true, true>, grid, block, s, a);
+        else if (shared)
+            timed_launch(&k_apply<T, R, NN, true>, grid, block, s, a);
+        else
+            timed_launch(&k_apply<T, R, NN, false>, grid, block, s, a);
+        return hipGetLastError();
+    };
+    if constexpr (R <= 8) return by_ni<1, 2, 3, 4>(apply_ni(R, nterms, shared), go);
+    else return by_ni<>(-1, go);
 }
 
 template <typename T>

@@ -442,6 +442,38 @@ int psgd_aggregate_mixed_comm(psgd_plan* plan, void* const* grads_bf16, void* co
 int psgd_plan_mixed_folds_comm(const psgd_plan* plan, int64_t step, int32_t world,
                                int32_t* fold_in, int32_t* fold_out);
 
+/* ------------------- ... with the averages stored at per-tensor destinations (DDP hook) -------- */
+/* The completion of the DDP communication hook with an fp32 residual of bf16 gradients. The hook
+ * adds every bucket into the residual when it arrives, so `residual` already holds residual +
+ * gradients: this call runs NO ADD and takes no bf16 source. DEFINED as this sequence, and equal
+ * to it bit for bit, with nothing else observable:
+ *   1. psgd_aggregate_comm(plan, residual, avg_f32, step, flat, unc_residual, flat_f32, comm): the
+ *      same kernels, collectives (order and count), residual, P/Q state and step semantics
+ *   2. dst_bf16[i][j] = bf16(avg_f32 of tensor i [j]), unc_dst_bf16[k][j] = bf16(flat_f32 of
+ *      tensor k [j])   round to nearest even
+ * dst_bf16 is in the plan's tensor order, unc_dst_bf16 in the flat plan's. Each pointer is 2-byte
+ * aligned or better (a parameter's view inside a DDP bucket, where parameters sit back to back)
+ * and addresses numel dense bf16 elements; nothing outside those numel elements is written. They
+ * are written, never accumulated into.
+ * Where the stages run: the final pass of the communicator sequence (as in
+ * psgd_aggregate_mixed_comm: k_apply with two term sets, k_lowrank_out after a fused k_final_odd,
+ * the world-size-1 k_apply for a 1-rank communicator) stores the bf16 rounding itself, at
+ * dst_bf16[tensor]. Its tiles, loads and arithmetic are laid out from the residual's alignment
+ * and the plan's offsets exactly as in step 1; only the store follows the destination: a vector
+ * tile whose destination (tensor base + row offset) is 8-byte aligned stores 8 bytes, any other
+ * four 2-byte elements, chosen once per tile; every store goes through a descriptor that spans
+ * the tile's rows of its own tensor. The flat tail is packed into the plan's fp32 staging buffer
+ * where psgd_aggregate_comm packs (stage = x / W, x = +0.0), all-reduced there, and rounded into
+ * unc_dst_bf16 by the leading workgroups of the final launch (a launch of its own after the
+ * world-size-1 instance).
+ * Eligibility, refusals and poisoning are exactly those of psgd_aggregate_mixed_comm, with the
+ * admission asked for the destination-table instances themselves. psgd_plan_mixed_folds_dst:
+ * fold_out 1 where the call would run at world size `world` (>= 1), 0 for an ineligible plan. */
+int psgd_aggregate_mixed_comm_dst(psgd_plan* plan, void* const* residual, void* const* dst_bf16,
+                                  int64_t step, psgd_flat* flat, void* const* unc_residual,
+                                  void* const* unc_dst_bf16, psgd_comm* comm, void* stream);
+int psgd_plan_mixed_folds_dst(const psgd_plan* plan, int64_t step, int32_t world, int32_t* fold_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,8 @@ _SIGNATURES = {
     "psgd_plan_mixed_folds": ([_vp, _i64, _P_i32, _P_i32], _i32),
     "psgd_aggregate_mixed_comm": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_plan_mixed_folds_comm": ([_vp, _i64, _i32, _P_i32, _P_i32], _i32),
+    "psgd_aggregate_mixed_comm_dst": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_mixed_folds_dst": ([_vp, _i64, _i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -253,6 +255,24 @@ class Plan:
         check(lib().psgd_aggregate_mixed_comm(self._h, grads_bf16, residual, out_ptr, step,
                                               flat._h if flat is not None else None, unc_bf16, unc_residual,
                                               flat_out or None, comm._h if comm is not None else None, stream))
+
+    # --- ... with the bf16 averages stored at per-tensor destinations (the DDP hook's completion)
+    def mixed_folds_dst(self, step: int, world: int) -> int:
+        """1 where ``aggregate_mixed_comm_dst`` would run ``step`` at world size ``world``
+        (psgd_plan_mixed_folds_dst), 0 for a plan the call refuses."""
+        fo = _i32()
+        check(lib().psgd_plan_mixed_folds_dst(self._h, step, world, ctypes.byref(fo)))
+        return int(fo.value)
+
+    def aggregate_mixed_comm_dst(self, residual, dst_bf16, step: int, comm: "Comm", stream: int, flat=None,
+                                 unc_residual=None, unc_dst_bf16=None) -> None:
+        """psgd_aggregate_mixed_comm_dst: ``residual`` (fp32, already holding residual + gradients)
+        through psgd_aggregate_comm, the bf16 averages stored at ``dst_bf16[i]`` / ``unc_dst_bf16[k]``.
+        Raises ``ValueError`` for a plan it does not serve, before anything is launched or any
+        collective issued."""
+        check(lib().psgd_aggregate_mixed_comm_dst(self._h, residual, dst_bf16, step,
+                                                  flat._h if flat is not None else None, unc_residual, unc_dst_bf16,
+                                                  comm._h if comm is not None else None, stream))
 
     # --- buckets of shape groups (W > 1 comm/compute overlap)
     def set_buckets(self, group_end: Sequence[int]) -> None:

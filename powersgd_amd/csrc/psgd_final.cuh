@@ -651,11 +651,16 @@ __global__ __launch_bounds__(FinNT<R>::value) __attribute__((amdgpu_waves_per_eu
 #define PSGD_LOWRANK_UR 4
 #endif
 constexpr int kLowrankUR = PSGD_LOWRANK_UR;
-template <typename T, int R, int NI, int V>
+// DST (psgd_aggregate_mixed_comm_dst, T = bf16_pin_t; kDstVec / kDstElem): the output goes to
+// a.odst[d.tensor], a tensor of any 2-byte alignment; the store form as in apply_tile (psgd_stream.cuh)
+template <typename T, int R, int NI, int V, int DST = 0>
 __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t) {
     const TileGeom g = tile_geom<V>(d, t);
     const int r = d.r;
-    const rsrc_t rO = make_rsrc(static_cast<T*>(a.out) + d.out_off + g.row_begin * g.m,
+    T* obase;
+    if constexpr (DST != 0) obase = static_cast<T*>(a.odst[d.tensor]);
+    else obase = static_cast<T*>(a.out) + d.out_off;
+    const rsrc_t rO = make_rsrc(obase + g.row_begin * g.m,
                                 uint32_t((g.row_end - g.row_begin) * g.m * int64_t(sizeof(T))));
     const int nt = NI > 0 ? NI : a.nterms;
     constexpr int NC = NI > 0 ? NI : 1;
@@ -692,7 +697,8 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
                     for (int v = 0; v < V; ++v) o[v] = o[v] + alpha * dotr<R>(pa[u][k], ba[k][v]);
                 if (g.active && row < g.row_end) {
                     const uint32_t off = uint32_t((row - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(T));
-                    st_vec<T>(rO, off, o);
+                    if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
+                    else st_vec<T>(rO, off, o);
                 }
             }
         }
@@ -720,7 +726,8 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
         }
         if (g.active) {
             const uint32_t off = uint32_t((row - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(T));
-            st_vec<T>(rO, off, o);
+            if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
+            else st_vec<T>(rO, off, o);
         }
     }
 }

@@ -493,6 +493,29 @@ hipError_t launch_lowrank_mix(int R, int nterms, const ApplyArgs& a, const MixAr
 hipError_t launch_flat_ingest(const FlatArgs& a, const MixArgs& x, hipStream_t s);
 hipError_t launch_flat_round(const FlatArgs& a, const MixArgs& x, hipStream_t s);
 
+// psgd_aggregate_mixed_comm_dst (the DDP hook's one-call form): the final pass of the
+// communicator sequence stores each tensor's bf16 average at the tensor's own destination (a view
+// into a DDP bucket: dense, 2-byte aligned or better) instead of a dense buffer at the plan's
+// output offsets. Device pointer tables: `dst` in the plan's tensor order (the launch functions
+// read it as ApplyArgs::odst), `unc_dst` in the flat plan's order (a kernel argument of its own
+// beside MixArgs, whose layout the existing instances keep). The tiles are laid out exactly as
+// the dense instances' (from the residual's alignment); only their stores follow the
+// destination's alignment (psgd_stream.cuh, apply_tile).
+struct MixDst {
+    void* const* dst;
+    void* const* unc_dst;
+};
+// psgd_mixed_dst.hip: the destination-table instances of launch_apply_mix_w, launch_lowrank_mix
+// and launch_apply_mix (`waves` as above). The first two carry a.flat's items as round items into
+// unc_dst, first; launch_apply_mix_dst (a 1-rank communicator's unfused final pass) takes none:
+// launch_flat_round_dst follows it as a launch of its own.
+hipError_t launch_apply_mix_w_dst(int R, int nterms, const ApplyArgs& a, const MixArgs& x, void* const* unc_dst,
+                                  int ntiles, hipStream_t s, int* waves);
+hipError_t launch_lowrank_mix_dst(int R, int nterms, const ApplyArgs& a, const MixArgs& x, void* const* unc_dst,
+                                  int ntiles, hipStream_t s, int* waves);
+hipError_t launch_apply_mix_dst(int R, int nterms, const ApplyArgs& a, int ntiles, hipStream_t s, int* waves);
+hipError_t launch_flat_round_dst(const FlatArgs& a, const MixArgs& x, void* const* unc_dst, hipStream_t s);
+
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),
 // then two parities x iterations slots of xchg_slot floats each; the producer kernels (k_reduce,

@@ -17,6 +17,10 @@
 // communicator, defined as the ADD, psgd_aggregate_comm on the residual and the GATHER. The output
 // fold alone, on every step (admission per communicator kind, admit_comm); the ADD is always a
 // launch of its own, first; the flat tail is staged in fp32 (Mixed::stage) around its collective.
+// psgd_aggregate_mixed_comm_dst / psgd_plan_mixed_folds_dst: the DDP hook's form of the same step.
+// The residual already holds residual + gradients (the hook adds each bucket on arrival), so the
+// call is psgd_aggregate_comm on the residual and the GATHER alone, and the final pass stores each
+// tensor's bf16 average at the tensor's own destination (MixDst): no ADD, no dense output.
 #include <memory>
 #include <string>
 
@@ -47,10 +51,10 @@ bool admitted(const psgd_plan* p, const IterRoute& r, const MixArgs& none) {
     int w = 0;
     return admitted(launch_final_pass(p, r, FinalArgs{}, &none, 0, nullptr, &w), w);
 }
-bool admitted(const psgd_plan* p, const OutRoute& o, const MixArgs& none) {
+bool admitted(const psgd_plan* p, const OutRoute& o, const MixArgs& none, const MixDst* dst = nullptr) {
     int w = 0;
     ApplyArgs aa{};
-    return admitted(launch_out_pass(p, o, aa, &none, 0, nullptr, &w), w);
+    return admitted(launch_out_pass(p, o, aa, &none, 0, nullptr, &w, dst), w);
 }
 
 // (Re-)ask the runtime about the mixed instances this plan's current tiling would launch: per
@@ -94,6 +98,27 @@ bool comm_eligible(const psgd_plan* p, int world) {
     return m.comm_out[one][0] && m.comm_out[one][1];
 }
 
+// psgd_aggregate_mixed_comm_dst: the destination-table instance of the same output pass, asked
+// for itself (its 2-byte store form is code the dense instance does not have); the routes read
+// what admit_comm's read, under a key of its own
+void admit_dst(psgd_plan* p) {
+    psgd_plan::Mixed& m = *p->mixed;
+    const uint64_t key = uint64_t(p->fin_ok) | uint64_t(uint32_t(p->out_nt)) << 8;
+    if (m.dst_key == key) return;
+    m.dst_key = key;
+    const MixArgs none{};
+    const MixDst tabs{};
+    for (int one = 0; one < 2; ++one)
+        for (int par = 0; par < 2; ++par)
+            m.dst_out[one][par] = admitted(p, p->out_route(par, one ? 1 : 2, comm_out_ctx(&none, &tabs)), none, &tabs);
+}
+
+bool dst_eligible(const psgd_plan* p, int world) {
+    const psgd_plan::Mixed& m = *p->mixed;
+    const int one = world == 1 ? 1 : 0;
+    return m.dst_out[one][0] && m.dst_out[one][1];
+}
+
 // The plan's mixed state: the bf16 gradients' pointer tables and the run-table ADD, device side in
 // one allocation of the plan's own (made once, by the first call on a bound plan)
 int ensure(psgd_plan* p) {
@@ -113,10 +138,11 @@ int ensure(psgd_plan* p) {
         return st;
     int64_t rb = 0;
     if (int st = psgd_runs_workspace_bytes(mx.add, &rb)) return st;
-    const size_t tab = align256(TableCache::bytes(nt));
-    PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&mx.dev), tab + size_t(rb)));
-    mx.add_ws = mx.dev + tab;
+    const size_t tab = align256(TableCache::bytes(nt));  // src_tab, then dst, then the ADD's workspace
+    PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&mx.dev), 2 * tab + size_t(rb)));
+    mx.add_ws = mx.dev + 2 * tab;
     mx.src_tab.bind(mx.dev, nt);
+    mx.dst.bind(mx.dev + tab, nt);
     return psgd_runs_bind(mx.add, p->device, mx.add_ws);
 }
 
@@ -130,20 +156,26 @@ void folds_at(const psgd_plan* p, int64_t step, int32_t* in, int32_t* out) {
     *in = eligible && single && m.fin_in ? 1 : 0;
 }
 
-// room for the uncompressed bf16 gradients' pointer table (first call, or a larger flat plan than
-// the last one's), and the null checks of both tensor lists
+// room for the uncompressed bf16 gradients' pointer table and, behind it, their destinations'
+// (first call, or a larger flat plan than the last one's), and the null checks of both tensor
+// lists (`unc`: the bf16 gradients, or the bf16 destinations of psgd_aggregate_mixed_comm_dst)
 int unc_table(psgd_plan::Mixed& m, psgd_flat* f, void* const* unc, void* const* unc_residual, hipStream_t s) {
-    if (size_t(f->count) > m.unc_cap) {
+    const size_t cnt = size_t(f->count);
+    if (cnt > m.unc_cap) {
         PSGD_HIP(hipStreamSynchronize(s));
         m.unc_tab.release();
+        m.unc_dst.release();
         if (m.unc_dev) PSGD_HIP(hipFree(m.unc_dev));
         m.unc_dev = nullptr;
-        PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&m.unc_dev), TableCache::bytes(size_t(f->count))));
-        m.unc_cap = size_t(f->count);
-        m.unc_tab.bind(m.unc_dev, size_t(f->count));
-    } else if (m.unc_tab.n != size_t(f->count)) {
+        m.unc_cap = 0;
+        PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&m.unc_dev), 2 * TableCache::bytes(cnt)));
+        m.unc_cap = cnt;
+        m.unc_tab.bind(m.unc_dev, cnt);
+        m.unc_dst.bind(m.unc_dev + TableCache::bytes(cnt), cnt);
+    } else if (m.unc_tab.n != cnt) {
         PSGD_HIP(hipStreamSynchronize(s));
-        m.unc_tab.bind(m.unc_dev, size_t(f->count));
+        m.unc_tab.bind(m.unc_dev, cnt);
+        m.unc_dst.bind(m.unc_dev + TableCache::bytes(cnt), cnt);
     }
     for (int32_t i = 0; i < f->count; ++i)
         if (!unc[i] || !unc_residual[i]) return fail(PSGD_ERR_VALUE, "null uncompressed tensor pointer");
@@ -213,6 +245,18 @@ int mixed_impl(psgd_plan* p, void* const* grads, void* const* residual, void* ou
     return aggregate_ctx(p, residual, step, s, c);
 }
 
+// the fp32 staging of the flat tail (first call, or a larger flat plan than the last one's)
+int stage_room(psgd_plan::Mixed& m, const psgd_flat* f, hipStream_t s) {
+    if (size_t(f->total) <= m.stage_cap) return PSGD_OK;
+    PSGD_HIP(hipStreamSynchronize(s));
+    if (m.stage) PSGD_HIP(hipFree(m.stage));
+    m.stage = nullptr;
+    m.stage_cap = 0;
+    PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&m.stage), size_t(f->total) * sizeof(float)));
+    m.stage_cap = size_t(f->total);
+    return PSGD_OK;
+}
+
 // psgd_aggregate_mixed_comm past its argument checks. *refused: the plan has no admitted instance
 // (nothing launched, no collective issued: the communicator stays usable)
 int mixed_comm_impl(psgd_plan* p, void* const* grads, void* const* residual, void* out, int64_t step, psgd_flat* f,
@@ -232,20 +276,42 @@ int mixed_comm_impl(psgd_plan* p, void* const* grads, void* const* residual, voi
     MixArgs x{};
     if (f) {
         if (int st = unc_table(m, f, unc, unc_residual, s)) return st;
-        if (size_t(f->total) > m.stage_cap) {  // (first call, or a larger flat plan than the last one's)
-            PSGD_HIP(hipStreamSynchronize(s));
-            if (m.stage) PSGD_HIP(hipFree(m.stage));
-            m.stage = nullptr;
-            m.stage_cap = 0;
-            PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&m.stage), size_t(f->total) * sizeof(float)));
-            m.stage_cap = size_t(f->total);
-        }
+        if (int st = stage_room(m, f, s)) return st;
         PSGD_HIP(m.unc_tab.select(unc, s));
         x.unc_src = m.unc_tab.table();
         x.stage = m.stage;
     }
     if (int st = psgd_runs_add_list(m.add, grads, residual, 1, s)) return st;
     return aggregate_comm_ctx(p, residual, out, step, f, unc_residual, flat_out, comm, s, &x);
+}
+
+// psgd_aggregate_mixed_comm_dst past its argument checks (`refused` as in mixed_comm_impl)
+int mixed_dst_impl(psgd_plan* p, void* const* residual, void* const* dst, int64_t step, psgd_flat* f,
+                   void* const* unc_residual, void* const* unc_dst, psgd_comm* comm, hipStream_t s, bool* refused) {
+    DevScope scope(p->device);
+    if (int st = ensure(p)) return st;
+    psgd_plan::Mixed& m = *p->mixed;
+    // the tiling the step will run on: the residual's alignment decides the vector layout, as in
+    // the three-stage flow; the destinations' alignment only picks the store form, in the kernel
+    if (int st = refresh_pointers(p, residual, s)) return st;
+    admit_dst(p);
+    if (!dst_eligible(p, comm_world(comm))) {
+        *refused = true;
+        return fail(PSGD_ERR_VALUE, "psgd_aggregate_mixed_comm_dst: no admitted destination-table instance of this "
+                                    "plan's final pass (two waves per SIMD, no scratch)");
+    }
+    MixArgs x{};
+    MixDst t{};
+    if (f) {
+        if (int st = unc_table(m, f, unc_dst, unc_residual, s)) return st;
+        if (int st = stage_room(m, f, s)) return st;
+        PSGD_HIP(m.unc_dst.select(unc_dst, s));
+        t.unc_dst = m.unc_dst.table();
+        x.stage = m.stage;
+    }
+    PSGD_HIP(m.dst.select(dst, s));
+    t.dst = m.dst.table();
+    return aggregate_comm_ctx(p, residual, nullptr, step, f, unc_residual, nullptr, comm, s, &x, &t);
 }
 
 }  // namespace
@@ -255,6 +321,8 @@ void psgd::mixed_release(psgd_plan* p) {
     psgd_plan::Mixed* m = p->mixed;
     m->src_tab.release();
     m->unc_tab.release();
+    m->dst.release();
+    m->unc_dst.release();
     if (m->add) (void)psgd_runs_destroy(m->add);
     if (m->dev) (void)hipFree(m->dev);
     if (m->unc_dev) (void)hipFree(m->unc_dev);
@@ -322,6 +390,37 @@ int psgd_aggregate_mixed_comm(psgd_plan* p, void* const* grads_bf16, void* const
                                    unc_residual, flat_out_bf16, comm, static_cast<hipStream_t>(stream), &refused);
     // a failure past the argument checks can leave this rank's collective sequence short of its
     // peers': the communicator refuses every later call (psgd_comm.cpp, comm_poison)
+    if (st && !refused) comm_poison(comm, psgd_last_error());
+    return st;
+}
+
+int psgd_plan_mixed_folds_dst(const psgd_plan* plan, int64_t step, int32_t world, int32_t* fold_out) {
+    if (!plan || !fold_out) return fail(PSGD_ERR_VALUE, "null argument");
+    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
+    if (world < 1) return fail(PSGD_ERR_VALUE, "world size must be >= 1");
+    *fold_out = 0;
+    if (ineligible(plan)) return PSGD_OK;
+    return query_folds(plan, admit_dst, [&](const psgd_plan* p) { *fold_out = dst_eligible(p, world) ? 1 : 0; });
+}
+
+int psgd_aggregate_mixed_comm_dst(psgd_plan* p, void* const* residual, void* const* dst_bf16, int64_t step,
+                                  psgd_flat* f, void* const* unc_residual, void* const* unc_dst_bf16, psgd_comm* comm,
+                                  void* stream) {
+    if (int st = check_call(p && residual && dst_bf16 && comm, p && p->bound, step >= 0, "step out of range")) return st;
+    const bool has_flat = f && f->total > 0;
+    if (has_flat)
+        if (int st = check_flat(f, unc_residual && unc_dst_bf16, f->dtype == PSGD_F32 && f->device == p->device,
+                                PSGD_ERR_VALUE, "psgd_aggregate_mixed_comm_dst takes an fp32 flat plan (the uncompressed "
+                                                "tensors' residual) on the codec's device"))
+            return st;
+    // eligibility, then every tensor's two pointers: the destinations are bf16 like the gradients
+    if (int st = check_tensors(p, dst_bf16, residual)) return st;
+    std::string why;
+    if (comm_poisoned(comm, &why))
+        return fail(PSGD_ERR_STATE, ("communicator unusable after an earlier failure: " + why).c_str());
+    bool refused = false;
+    const int st = mixed_dst_impl(p, residual, dst_bf16, step, has_flat ? f : nullptr, unc_residual, unc_dst_bf16, comm,
+                                  static_cast<hipStream_t>(stream), &refused);
     if (st && !refused) comm_poison(comm, psgd_last_error());
     return st;
 }

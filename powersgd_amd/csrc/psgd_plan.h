@@ -373,6 +373,13 @@ struct psgd_plan {
         bool comm_out[2][2] = {};
         float* stage = nullptr;
         size_t stage_cap = 0;      // floats
+        // psgd_aggregate_mixed_comm_dst: admission of the destination-table instances (a key of
+        // their own, indexed like comm_out), and the destinations' pointer tables, beside src_tab
+        // in `dev` and beside unc_tab in `unc_dev` (DDP rebuilds its buckets once: the pointers
+        // change after the first iteration and are stable from then on)
+        uint64_t dst_key = ~uint64_t(0);
+        bool dst_out[2][2] = {};
+        TableCache dst, unc_dst;
     };
     Mixed* mixed = nullptr;
     int64_t xslot_off(int64_t step, int it) const {  // byte offset of a slot in every buffer
@@ -491,6 +498,9 @@ struct StepCtx {
     // instance with these arguments; mix_in: the single-pass final kernel also ingests (ingest fold)
     const MixArgs* mix = nullptr;
     bool mix_in = false;
+    // psgd_aggregate_mixed_comm_dst: the mixed output pass stores at these per-tensor destinations
+    // (its destination-table instances) instead of `out`
+    const MixDst* dst = nullptr;
 };
 
 // The contexts of the two one-call steps, shared by the drivers and by admission (psgd_mixed.cpp):
@@ -500,9 +510,10 @@ inline StepCtx world1_ctx(StepCtx c) {
     c.fuse = c.write_out = true;
     return c;
 }
-inline StepCtx comm_out_ctx(const MixArgs* mix) {
+inline StepCtx comm_out_ctx(const MixArgs* mix, const MixDst* dst = nullptr) {
     StepCtx c;
     c.mix = mix;
+    c.dst = dst;
     return c;
 }
 
@@ -557,6 +568,7 @@ struct OutRoute {
     int32_t out_nt;   // output stores nt only (world size 1, large plans)
     bool timed;       // benchmark timing covers this launch
     bool flat;        // the context's flat items ride in the launch (k_lowrank_out takes none)
+    bool dst;         // Mix / MixW / the mixed Lowrank: the destination-table instance (MixDst)
     int reduced_slot; // history slot of the earlier iterations' reduced factors (1: never copied to 2)
 };
 
@@ -567,7 +579,7 @@ struct OutRoute {
 hipError_t launch_final_pass(const psgd_plan* p, const IterRoute& r, const FinalArgs& a, const MixArgs* mix, int ntiles,
                              hipStream_t s, int* waves);
 hipError_t launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArgs& a, const MixArgs* mix, int ntiles,
-                           hipStream_t s, int* waves);
+                           hipStream_t s, int* waves, const MixDst* dst = nullptr);
 
 // psgd_step.cpp
 int refresh_pointers(psgd_plan* p, void* const* grads, hipStream_t stream);
@@ -582,9 +594,10 @@ void ipc_release(psgd_plan* p);
 void mixed_release(psgd_plan* p);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
 int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
-// psgd_step.cpp: the world-size-W step of psgd_aggregate_comm; with `mix`, of psgd_aggregate_mixed_comm
+// psgd_step.cpp: the world-size-W step of psgd_aggregate_comm; with `mix`, of psgd_aggregate_mixed_comm;
+// with `mix` and `dst`, of psgd_aggregate_mixed_comm_dst (`out` and `flat_out` unused)
 int aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
-                       void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix);
+                       void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix, const MixDst* dst = nullptr);
 
 }  // namespace psgd
 
@@ -632,6 +645,7 @@ inline OutRoute psgd_plan::out_route(int64_t step, int world, const StepCtx& c) 
     o.out_nt = world == 1 ? out_nt : 0;
     o.timed = o.kind == OutRoute::Apply;
     o.flat = o.kind == OutRoute::Apply || c.mix != nullptr;
+    o.dst = c.mix != nullptr && c.dst != nullptr;
     // fused (world size 1): the reduced factor was never copied to history slot 2
     o.reduced_slot = fused_norm(c.fuse, 1) ? 1 : 2;
     return o;

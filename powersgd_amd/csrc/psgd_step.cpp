@@ -511,9 +511,15 @@ hipError_t psgd::launch_final_pass(const psgd_plan* p, const IterRoute& r, const
 }
 
 hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArgs& a, const MixArgs* mix, int ntiles,
-                                 hipStream_t s, int* waves) {
+                                 hipStream_t s, int* waves, const MixDst* dst) {
     a.out_nt = o.out_nt;
     const int R = p->rbucket, I = p->iters;
+    if (o.dst) {  // psgd_aggregate_mixed_comm_dst: the averages go to the per-tensor destinations
+        a.odst = dst->dst;
+        if (o.kind == OutRoute::Lowrank) return launch_lowrank_mix_dst(R, I, a, *mix, dst->unc_dst, ntiles, s, waves);
+        if (o.inst == OutRoute::MixW) return launch_apply_mix_w_dst(R, I, a, *mix, dst->unc_dst, ntiles, s, waves);
+        return launch_apply_mix_dst(R, I, a, ntiles, s, waves);
+    }
     if (o.kind == OutRoute::Lowrank)
         return mix ? launch_lowrank_mix(R, I, a, *mix, ntiles, s, waves) : launch_lowrank_out(p->dtype, R, I, a, ntiles, s);
     switch (o.inst) {
@@ -573,7 +579,7 @@ int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t s
     if (o.timed)
         if (int st = timing_begin(p, s, &ev, true)) return st;
     TimedScope ts(ev);
-    PSGD_HIP(launch_out_pass(p, o, aa, c.mix, nt, s, nullptr));
+    PSGD_HIP(launch_out_pass(p, o, aa, c.mix, nt, s, nullptr, c.dst));
     return PSGD_OK;
 }
 
@@ -616,18 +622,25 @@ int refresh_table(psgd_plan* p, void* const* ptrs, TableCache& tab, hipStream_t 
 
 // `mix` (psgd_aggregate_mixed_comm): `grads` the fp32 residual, `out` / `flat_out` bf16, `unc` the
 // uncompressed tensors' fp32 residual; the flat tail is staged in mix->stage (fp32) around its
-// collective: ingest-pack in a launch of its own first, the round items in the final launch
+// collective: ingest-pack in a launch of its own first, the round items in the final launch.
+// `mix` and `dst` (psgd_aggregate_mixed_comm_dst): `grads` already holds residual + gradients, so
+// nothing is ingested: the flat tail is packed as psgd_aggregate_comm packs it (x / W, x = +0.0,
+// flat_pack_item<float>), with mix->stage as its flat buffer, and the round items store into
+// dst->unc_dst
 int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f,
-                             void* const* unc, void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix) {
+                             void* const* unc, void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix,
+                             const MixDst* dst) {
     const bool has_flat = f != nullptr;
     const int world = comm_world(comm);
     // x / W into the flat buffer, x = 0 (utils.py:43-47, powersgd.py:29-30): inside the first
     // even product's launch when the step starts even, else its own launch
     FlatArgs fa{};
-    const bool fold = has_flat && !mix && p->even(step, 0) && !p->wide();  // wide products carry no flat pack
+    const bool ingest = mix && !dst;
+    const bool fold = has_flat && !ingest && p->even(step, 0) && !p->wide();  // wide products carry no flat pack
     if (fold || (mix && has_flat)) {
-        if (int st = flat_args(f, unc, flat_out, world, s, &fa)) return st;
-        if (mix) PSGD_HIP(launch_flat_ingest(fa, *mix, s));
+        if (int st = flat_args(f, unc, dst ? static_cast<void*>(mix->stage) : flat_out, world, s, &fa)) return st;
+        if (ingest) PSGD_HIP(launch_flat_ingest(fa, *mix, s));
+        else if (!fold) PSGD_HIP(launch_flat_pack(f->dtype, fa, s));
     } else if (has_flat) {
         if (int st = psgd_flat_pack(f, unc, flat_out, world, s)) return st;
     }
@@ -642,7 +655,7 @@ int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_
                                     last && has_flat ? tail : nullptr, last && has_flat ? size_t(f->total) : 0, s))
             return st;
     }
-    StepCtx d = comm_out_ctx(mix);
+    StepCtx d = comm_out_ctx(mix, dst);
     if (!mix) return decompress_impl(p, grads, out, step, world, s, d);
     // the round items ride in every final launch built for them; a 1-rank communicator's unfused
     // final pass is the world-size-1 instance, whose flat items ingest: the round follows it
@@ -650,7 +663,7 @@ int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_
     const bool ride = o.kind == OutRoute::Lowrank || o.inst == OutRoute::MixW;
     d.fl = has_flat && ride ? &fa : nullptr;
     if (int st = decompress_impl(p, grads, out, step, world, s, d)) return st;
-    if (has_flat && !ride) PSGD_HIP(launch_flat_round(fa, *mix, s));
+    if (has_flat && !ride) PSGD_HIP(dst ? launch_flat_round_dst(fa, *mix, dst->unc_dst, s) : launch_flat_round(fa, *mix, s));
     return PSGD_OK;
 }
 

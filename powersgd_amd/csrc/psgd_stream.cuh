@@ -172,6 +172,18 @@ struct StIo<bf16_pin_t> {
         asm volatile("" : "+v"(x));
         StIo<bf16_t>::template st1<AUX>(r, off, __uint_as_float(x));
     }
+    // The destination-table instances (psgd_aggregate_mixed_comm_dst, psgd_mixed_dst.hip) on a
+    // destination that is not 8-byte aligned (a tensor inside a DDP bucket is 2-byte aligned in
+    // general): the four values pinned exactly as st4 pins them, then four 2-byte stores
+    template <int AUX = PSGD_ST_AUX>
+    static __device__ __forceinline__ void st4e(rsrc_t r, uint32_t off, const float (&v)[4]) {
+        typedef unsigned v4u __attribute__((ext_vector_type(4)));
+        v4u x = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+        asm volatile("" : "+v"(x));
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            StIo<bf16_t>::template st1<AUX>(r, off + 2u * uint32_t(e), __uint_as_float(x[e]));
+    }
 };
 // V consecutive elements at byte offset `off` of descriptor r
 template <typename T, int AUX = PSGD_ST_AUX>
@@ -181,6 +193,26 @@ __device__ __forceinline__ void st_vec(rsrc_t r, uint32_t off, const float (&v)[
 template <typename T, int AUX = PSGD_ST_AUX>
 __device__ __forceinline__ void st_vec(rsrc_t r, uint32_t off, const float (&v)[1]) {
     StIo<T>::template st1<AUX>(r, off, v[0]);
+}
+// The destination-table instances (psgd_aggregate_mixed_comm_dst): DST selects the store form of a
+// tile whose bf16 output goes to a per-tensor destination of any 2-byte alignment. kDstVec: the
+// dense instance's stores (8 bytes per vector); kDstElem: a vector as four 2-byte stores. The
+// kernel picks the instance per tile (dst_al8: workgroup-uniform); the tile's layout, loads and
+// arithmetic are the same in both and in the dense instance (DST = 0).
+// The four 2-byte stores of kDstElem always take nt alone (kStAuxOutNt): written through (sc0 | nt |
+// sc1) every 2-byte store leaves the L2 as a partial line of its own, and the final pass of the
+// ResNet-50 hook completion ran 0.21 ms against 0.11 ms with 8-byte stores; with nt alone the L2
+// merges a lane's four stores and its neighbours' (0.120 against 0.118 ms, the 1-rank
+// communicator's ONT instance). The cache policy changes no bit.
+constexpr int kDstVec = 1, kDstElem = 2;
+template <int DST, int AUX = PSGD_ST_AUX>
+__device__ __forceinline__ void st_vec_dst(rsrc_t r, uint32_t off, const float (&v)[4]) {
+    if constexpr (DST == kDstElem) StIo<bf16_pin_t>::template st4e<kStAuxOutNt>(r, off, v);
+    else StIo<bf16_pin_t>::template st4<AUX>(r, off, v);
+}
+template <int DST, int AUX = PSGD_ST_AUX>
+__device__ __forceinline__ void st_vec_dst(rsrc_t r, uint32_t off, const float (&v)[1]) {
+    StIo<bf16_pin_t>::template st1<AUX>(r, off, v[0]);
 }
 
 template <typename T>
@@ -451,14 +483,21 @@ __device__ __forceinline__ void flat_ingest_item(const FlatArgs& a, void* const*
 
 // Round: flat (bf16) = f2bf(stage), round to nearest even: the run-table GATHER of the three-stage
 // flow on the item's elements of the all-reduced flat tail.
-template <int NT>
-__device__ __forceinline__ void flat_round_item(const FlatArgs& a, const float* stage, int item) {
+// DST (psgd_aggregate_mixed_comm_dst): the item's elements go to the tensor's own destination
+// dst[en.tensor] (the flat plan's order; 2-byte aligned, element stores as here) instead of the
+// dense bf16 flat buffer; the descriptor spans the item's elements of that tensor alone.
+template <int NT, bool DST = false>
+__device__ __forceinline__ void flat_round_item(const FlatArgs& a, const float* stage, int item,
+                                                void* const* dst = nullptr) {
     constexpr int PER = kFlatItem / NT;
     const FlatItem it = a.items[item];
     const FlatEntry en = a.entries[it.entry];
     const gptr<const float> x = gconst<float>(stage) + en.off;
     const uint32_t cnt = uint32_t(en.numel - it.start < kFlatItem ? en.numel - it.start : kFlatItem);
-    const rsrc_t rf = make_rsrc(static_cast<bf16_t*>(a.flat) + en.off + it.start, cnt * 2u);
+    bf16_t* fbase;
+    if constexpr (DST) fbase = static_cast<bf16_t*>(dst[en.tensor]) + it.start;
+    else fbase = static_cast<bf16_t*>(a.flat) + en.off + it.start;
+    const rsrc_t rf = make_rsrc(fbase, cnt * 2u);
     float v[PER];
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
@@ -472,6 +511,15 @@ __device__ __forceinline__ void flat_round_item(const FlatArgs& a, const float* 
         const int64_t j = it.start + int64_t(q) * NT + threadIdx.x;
         if (j < en.numel) StIo<bf16_t>::st1(rf, uint32_t(int64_t(q) * NT + threadIdx.x) * 2u, v[q]);
     }
+}
+
+// The store form of a vector tile (m % 4 == 0) of the destination-table instances: true when the
+// tile's first destination element (tensor base + row offset; every row of the tile then) is
+// 8-byte aligned. Workgroup-uniform: one test per tile.
+__device__ __forceinline__ bool dst_al8(const ApplyArgs& a, const MatDesc& d, const Tile& t) {
+    const uintptr_t o = reinterpret_cast<uintptr_t>(a.odst[d.tensor]) +
+                        uintptr_t(int64_t(t.chunk) * d.chunk_rows * d.m) * sizeof(bf16_t);
+    return (o & 7) == 0;
 }
 
 struct TileGeom {
@@ -1142,7 +1190,12 @@ hipError_t dispatch_odd_mfma(int R, int nres, const ProductArgs& a, int ntiles, 
 
 // ------------------------------------------------------------------ apply ---------
 // TO: the output's element type (the gradient's; bf16 over an fp32 residual in the mixed instances)
-template <typename T, int R, int NI, bool SHARED, int V, bool ONT = false, typename TO = T>
+// DST (psgd_aggregate_mixed_comm_dst, TO = bf16_pin_t): the output goes to a.odst[d.tensor], a
+// tensor of any 2-byte alignment (a view into a DDP bucket). The tile's layout (V, from the
+// residual's alignment and the plan's offsets), its loads and its arithmetic stay those of the
+// dense instance; only the store of a vector tile follows the destination (kDstVec / kDstElem,
+// picked per tile by the kernel with dst_al8).
+template <typename T, int R, int NI, bool SHARED, int V, bool ONT = false, typename TO = T, int DST = 0>
 __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t) {
     const TileGeom g = tile_geom<V>(d, t);
     const int r = d.r;
@@ -1246,7 +1299,10 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
             if (g.active && row + u * g.stride < g.row_end) {
                 const uint32_t eo = uint32_t((b.rc[u] - g.row_begin) * g.m + g.col0);
                 st_vec<T>(rD, eo * uint32_t(sizeof(T)), b.x[u]);
-                st_vec<TO, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
+                if constexpr (DST != 0)
+                    st_vec_dst<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
+                else
+                    st_vec<TO, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
             }
         }
     };

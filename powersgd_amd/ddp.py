@@ -41,6 +41,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .powersgd import Config, PowerSGD, _DTYPES, _psgd_host, _require_device, _stream
+from .utils import is_distributed
 
 
 class _BucketRuns:
@@ -68,9 +69,20 @@ class PowerSGDState:
     component below 2^-8 of the element it lands on), the codec and the uncompressed average run
     in fp32 on the residual, and DDP gets the bf16 rounding of the fp32 average back. ``None``
     (default): the residual has the parameters' dtype. 4 bytes of state per parameter instead
-    of 2."""
+    of 2.
 
-    def __init__(self, config: Config, params, process_group=None, residual_dtype=None):
+    ``fused=True`` (bfloat16 parameters with ``residual_dtype=torch.float32`` only) completes an
+    iteration in ONE library call wherever it applies (psgd_aggregate_mixed_comm_dst, include/
+    psgd.h): the codec's final pass stores the bf16 rounding of each parameter's average straight
+    into that parameter's view of its DDP bucket, so no fp32 output slab is written and no
+    per-bucket gather runs. Bit for bit the three stages it replaces. It applies on a compressing
+    step, in a process group that runs over the library's own communicator (not ``PSGD_COMM=ipc`` /
+    ``torch``, not gloo), on a plan the call serves (rank bucket 1 / 2 / 4); every other
+    completion runs the three stages (``fused_folds()`` tells which)."""
+
+    fused = False  # (class default: the three-stage completion)
+
+    def __init__(self, config: Config, params, process_group=None, residual_dtype=None, fused=False):
         if process_group is not None and process_group is not dist.group.WORLD:
             raise ValueError("powersgd_hook all-reduces on the default process group (reference :207)")
         self.config = config
@@ -90,6 +102,10 @@ class PowerSGDState:
                                                and p0.dtype in (torch.float32, torch.bfloat16)):
             raise ValueError(f"residual_dtype must be None, or torch.float32 with float32 / bfloat16 parameters; "
                              f"got {residual_dtype} with {p0.dtype} parameters")
+        self.fused = bool(fused)
+        if self.fused and not (p0.dtype == torch.bfloat16 and residual_dtype == torch.float32):
+            raise ValueError(f"fused=True needs bfloat16 parameters with residual_dtype=torch.float32; got "
+                             f"{p0.dtype} parameters with residual_dtype={residual_dtype}")
         self._dev_index = _require_device(p0.device)
         if p0.dtype not in _DTYPES:
             raise RuntimeError(f"powersgd_hook supports float32, bfloat16 and float64 gradients, got {p0.dtype}")
@@ -115,6 +131,10 @@ class PowerSGDState:
         self._seen = [False] * len(self.params)
         self._nseen = 0
         self._pending: List[tuple] = []
+        # fused: per parameter its gradient view inside the pending bucket (the destination of its
+        # average), and their native split by the compression mask (built by the first fused completion)
+        self._dst: List[Optional[torch.Tensor]] = [None] * len(self.params)
+        self._dst_table = None
 
     def _arrive(self, bucket: "dist.GradBucket") -> "torch.futures.Future[torch.Tensor]":
         fut: torch.futures.Future = torch.futures.Future()
@@ -140,6 +160,9 @@ class PowerSGDState:
             for i in idx:
                 self._seen[i] = True
                 self._nseen += 1
+            if self.fused:
+                for i, g in zip(idx, grads):
+                    self._dst[i] = g.view(self.params[i].shape)
             self._pending.append((buf, runs, fut))
             if self._nseen == len(self.params):
                 self._complete()
@@ -161,6 +184,7 @@ class PowerSGDState:
         pending, self._pending = self._pending, []
         self._seen = [False] * len(self.params)
         self._nseen = 0
+        self._dst = [None] * len(self.params)
         for *_, f in pending:
             if not f.done():
                 f.set_exception(err)
@@ -195,7 +219,63 @@ class PowerSGDState:
         for buf, runs, _ in pending:
             runs.runs.gather(buf.data_ptr(), ctypes.addressof(self._out_ptrs), stream)
 
+    def _fused_comm(self):
+        """The library's own communicator when this process group runs over it (``PowerSGD.aggregate``'s
+        choice: RCCL, not ``PSGD_COMM=ipc`` / ``torch``, not gloo), else None. Collective on first use."""
+        codec = self.powersgd._powersgd
+        if not is_distributed() or codec._ipc_mode():
+            return None
+        return codec._rccl_comm()
+
+    def _fused_applies(self) -> bool:
+        """The completion about to run compresses, over the library's communicator, on a plan
+        psgd_aggregate_mixed_comm_dst serves (both step parities: a plan is eligible as a whole)."""
+        inner = self.powersgd
+        if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
+            return False
+        comm = self._fused_comm()
+        if comm is None:
+            return False
+        plan = inner._powersgd._plan
+        return plan.mixed_folds_dst(0, comm.world) == 1 and plan.mixed_folds_dst(1, comm.world) == 1
+
+    def fused_folds(self):
+        """``(fold_in, fold_out)`` of the NEXT completion: ``(0, 1)`` when it takes the one-call form
+        (the bf16 rounding of the averages runs inside the codec's final pass; the per-bucket ADD is
+        never folded: it runs at bucket arrival, under backward), ``(0, 0)`` when it runs the three
+        stages (``fused=False``, a warm-up step, another transport, a plan the call refuses)."""
+        return (0, 1) if self.fused and self._fused_applies() else (0, 0)
+
+    def _complete_fused(self) -> None:
+        """``PowerSGD.aggregate`` of the codec on the residual views as one library call: the same
+        bookkeeping (both step counters, the split by the compression mask), the bf16 averages
+        stored by the final pass into the pending buckets' gradient views. No ``_gather``."""
+        inner, codec = self.powersgd, self.powersgd._powersgd
+        if self._dst_table is None:
+            self._dst_table = _psgd_host.PtrTable([list(v.shape) for v in self.views], inner.is_compressed_mask,
+                                                  _lib.PSGD_BF16, self._dev_index)
+        self._dst_table.fill(self._dst)
+        inner.step_counter += 1
+        inner._table.fill(self.views)
+        kw = {}
+        if inner._unc is not None:
+            kw = dict(flat=inner._unc.plan, unc_residual=inner._table.unc_addr(),
+                      unc_dst_bf16=self._dst_table.unc_addr())
+        codec._plan.aggregate_mixed_comm_dst(inner._table.comp_addr(), self._dst_table.comp_addr(), codec.step_counter,
+                                             self._fused_comm(), _stream(self.residual.device), **kw)
+        codec.step_counter += 1
+        pending, self._pending = self._pending, []
+        self._seen = [False] * len(self.params)
+        self._nseen = 0
+        self._dst = [None] * len(self.params)
+        for buf, _, fut in pending:
+            fut.set_result(buf)
+
     def _complete(self) -> None:
+        if self.fused:
+            if self._fused_applies():
+                return self._complete_fused()
+            self._dst = [None] * len(self.params)
         outs = self.powersgd.aggregate(self.views)  # leaves the new residual in self.views
         pending, self._pending = self._pending, []
         self._seen = [False] * len(self.params)

@@ -474,6 +474,51 @@ int psgd_aggregate_mixed_comm_dst(psgd_plan* plan, void* const* residual, void* 
                                   void* const* unc_dst_bf16, psgd_comm* comm, void* stream);
 int psgd_plan_mixed_folds_dst(const psgd_plan* plan, int64_t step, int32_t world, int32_t* fold_out);
 
+/* ------------------- ... over the IPC exchange (psgd_ipc_*), in one call ----------------------- */
+/* The mixed forms of psgd_aggregate_ipc: world size W over the plan's open exchange session, no
+ * communicator, no host barrier. Each is DEFINED as a sequence of existing calls and equal to it
+ * bit for bit, with nothing else observable.
+ * psgd_aggregate_mixed_ipc (arguments as psgd_aggregate_mixed_comm without the communicator):
+ *   1. residual[i][j] += float(grads_bf16[i][j]), grads_bf16[i][j] = +0.0; the uncompressed
+ *      tensors likewise: unc_residual += float(unc_bf16), unc_bf16 = +0.0
+ *   2. psgd_aggregate_ipc(plan, residual, avg_f32, step, flat, unc_residual, flat_f32): the same
+ *      kernels, the same exchanges with the same flags and epochs
+ *   3. out_bf16 = bf16(avg_f32), flat_out_bf16 = bf16(flat_f32)   round to nearest even
+ * psgd_aggregate_mixed_ipc_dst (arguments as psgd_aggregate_mixed_comm_dst without the
+ * communicator; `residual` already holds residual + gradients, NO ADD, no dense output):
+ *   1. psgd_aggregate_ipc(plan, residual, avg_f32, step, flat, unc_residual, flat_f32)
+ *   2. dst_bf16[i][j] = bf16(avg_f32 of tensor i [j]), unc_dst_bf16[k][j] = bf16(flat_f32 of
+ *      tensor k [j]); nothing outside a destination's numel elements is written
+ * Where the stages run:
+ *   ingest       never folded: the dense form launches the run-table ADD first.
+ *   flat tail    packed straight into this rank's last exchange slot (dense form: slot = (x +
+ *                float(g)) / W, x = g = +0.0 in a launch of its own; _dst form: slot = x / W,
+ *                x = +0.0 where psgd_aggregate_ipc packs, inside the first even product's launch
+ *                on steps that start even). The LAST exchange sums the W slots' flat regions per
+ *                flat item in rank order and stores bf16(sum) at flat_out_bf16 / unc_dst_bf16
+ *                itself (k_xchg_mix): no fp32 staging buffer, no fp32 copy of the flat sums, no
+ *                round pass. A step without uncompressed tensors launches k_xchg alone.
+ *   output fold  every step: the output pass after the exchanges stores bf16 (the instances of
+ *                psgd_aggregate_mixed_comm / _comm_dst: k_apply with two term sets, k_lowrank_out
+ *                after a fused k_final_odd, the world-size-1 k_apply in a 1-rank session).
+ * Eligible: as psgd_aggregate_mixed_comm / _comm_dst (a bound PSGD_F32 plan, rank bucket 1, 2 or
+ * 4, not wide, one bucket, the final-pass instance of BOTH step parities admitted for the
+ * session's world size: psgd_plan_mixed_folds_comm / psgd_plan_mixed_folds_dst answer for it), with
+ * an open exchange session (psgd_ipc_open), flat->total within the session's flat_numel,
+ * step < 2^32 - 1 and no timed-out wait pending. An ineligible plan, an oversized flat plan, an
+ * out-of-range step and a null pointer: PSGD_ERR_VALUE; no session, or a timed-out wait
+ * (psgd_ipc_status): PSGD_ERR_STATE. The argument errors (a null argument, step < 0) are reported
+ * before the plan's state (an unbound plan: PSGD_ERR_STATE), then the plan's eligibility, then the
+ * session's state. Every refusal comes before anything is launched: gradients,
+ * residual and P/Q state stay as they were and the session stays usable. After a wait of this call
+ * times out, its bf16 outputs (flat tail included) hold NaN, as psgd_aggregate_ipc's fp32 ones. */
+int psgd_aggregate_mixed_ipc(psgd_plan* plan, void* const* grads_bf16, void* const* residual,
+                             void* out_bf16, int64_t step, psgd_flat* flat, void* const* unc_bf16,
+                             void* const* unc_residual, void* flat_out_bf16, void* stream);
+int psgd_aggregate_mixed_ipc_dst(psgd_plan* plan, void* const* residual, void* const* dst_bf16,
+                                 int64_t step, psgd_flat* flat, void* const* unc_residual,
+                                 void* const* unc_dst_bf16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,8 @@ _SIGNATURES = {
     "psgd_plan_mixed_folds_comm": ([_vp, _i64, _i32, _P_i32, _P_i32], _i32),
     "psgd_aggregate_mixed_comm_dst": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_plan_mixed_folds_dst": ([_vp, _i64, _i32, _P_i32], _i32),
+    "psgd_aggregate_mixed_ipc": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_aggregate_mixed_ipc_dst": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -312,6 +314,27 @@ class Plan:
     def aggregate_ipc(self, grads, out_ptr: int, step: int, flat, unc, flat_out: int, stream: int) -> None:
         check(lib().psgd_aggregate_ipc(self._h, grads, out_ptr, step, flat._h if flat else None, unc, flat_out,
                                        stream))
+
+    # --- ... with the fp32 residual of bf16 gradients folded in (the mixed forms of aggregate_ipc)
+    def aggregate_mixed_ipc(self, grads_bf16, residual, out_ptr: int, step: int, stream: int, flat=None,
+                            unc_bf16=None, unc_residual=None, flat_out: int = 0) -> None:
+        """psgd_aggregate_mixed_ipc: the ADD, ``aggregate_ipc`` on the residual and the bf16 GATHER in
+        one call over the plan's open exchange session. Eligible where ``mixed_folds_comm`` reports
+        (0, 1) at the session's world size. Raises ``ValueError`` for a plan it does not serve and
+        ``RuntimeError`` without a session or after a timed-out wait, before anything is launched."""
+        check(lib().psgd_aggregate_mixed_ipc(self._h, grads_bf16, residual, out_ptr, step,
+                                             flat._h if flat is not None else None, unc_bf16, unc_residual,
+                                             flat_out or None, stream))
+
+    def aggregate_mixed_ipc_dst(self, residual, dst_bf16, step: int, stream: int, flat=None, unc_residual=None,
+                                unc_dst_bf16=None) -> None:
+        """psgd_aggregate_mixed_ipc_dst: ``residual`` (fp32, already holding residual + gradients)
+        through ``aggregate_ipc``, the bf16 averages stored at ``dst_bf16[i]`` / ``unc_dst_bf16[k]``.
+        Eligible where ``mixed_folds_dst`` reports 1 at the session's world size; refusals as
+        ``aggregate_mixed_ipc``."""
+        check(lib().psgd_aggregate_mixed_ipc_dst(self._h, residual, dst_bf16, step,
+                                                 flat._h if flat is not None else None, unc_residual, unc_dst_bf16,
+                                                 stream))
 
     def ipc_status(self) -> bool:
         """True if a device-side wait timed out since the exchange was opened (synchronous; sticky

@@ -566,4 +566,20 @@ struct XchgArgs {
 };
 hipError_t launch_xchg(const XchgArgs& a, hipStream_t s);  // psgd_xchg.hip
 
+// The LAST exchange of psgd_aggregate_mixed_ipc[_dst] when the step has a flat tail (k_xchg_mix,
+// psgd_xchg_mix.hip): the factor exactly as k_xchg (never the item / Gram form: those belong to
+// non-last iterations), the flat region of the slot (XchgArgs::flat_off, the flat plan's layout)
+// summed per flat item and stored as bf16 where the averages belong: the dense bf16 flat buffer
+// at the flat plan's offsets (`flat_out`), or each tensor's own destination (`unc_dst`, the flat
+// plan's order: the destination-table form). No fp32 copy of the flat sums exists (XchgArgs::
+// flat_dst unused).
+struct XchgMixArgs {
+    const FlatEntry* entries;
+    const FlatItem* items;
+    int32_t nitems;
+    void* flat_out;          // bf16, dense form
+    void* const* unc_dst;    // bf16 destinations, destination-table form
+};
+hipError_t launch_xchg_mix(const XchgArgs& a, const XchgMixArgs& m, bool dst, hipStream_t s);
+
 }  // namespace psgd

@@ -146,6 +146,115 @@ void psgd::ipc_release(psgd_plan* p) {
     p->ipc_buf = nullptr;
 }
 
+int psgd::ipc_check(const psgd_plan* p, int64_t step) {
+    if (p->ipc_peer.empty()) return fail(PSGD_ERR_STATE, "psgd_ipc_open first");
+    // a wait of an earlier step gave up: that step's sums were invalid and the two-parity slot
+    // reuse is no longer safe, so every later step is refused (the ranks have drifted apart)
+    if (p->xerr_set())
+        return fail(PSGD_ERR_STATE, "an earlier IPC exchange wait timed out (a peer did not arrive within "
+                                    "PSGD_IPC_SPIN); the exchange is invalid until psgd_ipc_close");
+    if (step < 0 || step >= 0xffffffffLL) return fail(PSGD_ERR_VALUE, "step out of range (epochs are 32-bit)");
+    return PSGD_OK;
+}
+
+// World size W over the IPC exchange (include/psgd.h): per iteration the codec kernels (the
+// reduction or fused final pass also writes the local factor into this rank's exchange slot),
+// then k_xchg (flag, bounded wait for the peers' flags, rank-order SUM into the state buffer; the
+// last one also sums the uncompressed tensors packed /W into flat_out), then the output pass.
+// Nothing leaves the stream: no host barrier, no host synchronisation.
+// `mix` (psgd_aggregate_mixed_ipc): the flat tail is ingest-packed into the slot in a launch of its
+// own first (flat_ingest_item, the slot as its stage), the last exchange is k_xchg_mix (the flat
+// sums stored as bf16 into `flat_out`) and the output pass runs its bf16-output instance with no
+// flat items. `mix` and `dst` (psgd_aggregate_mixed_ipc_dst): `grads` already holds residual +
+// gradients, so the flat tail is packed as without `mix`, and both stores follow dst's tables.
+// Every other launch, flag and epoch is the same in the three forms.
+int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
+                            void* flat_out, hipStream_t s, const MixArgs* mix, const MixDst* dst) {
+    const bool has_flat = f != nullptr;
+    const int world = p->ipc_world;
+    const int last = p->iters - 1;
+    static const uint32_t spin = uint32_t(std::min<int64_t>(env_int("PSGD_IPC_SPIN", int64_t(1) << 26), 0xffffffffLL));
+    // x / W into this rank's last slot: inside the first even product's launch when the step
+    // starts even, else its own launch
+    FlatArgs fa{};
+    const bool ingest = mix && !dst;
+    const bool fold = has_flat && !ingest && p->even(step, 0);
+    float* flat_slot = p->xslot(step, last) + p->ipc_flat_off;
+    if (has_flat) {
+        if (int st = flat_args(f, unc, flat_slot, world, s, &fa)) return st;
+        if (ingest) {
+            MixArgs in = *mix;
+            in.stage = flat_slot;  // its stores are write-through (kStAuxSlot), as the pack's
+            PSGD_HIP(launch_flat_ingest(fa, in, s));
+        } else if (!fold) {
+            PSGD_HIP(launch_flat_pack(f->dtype, fa, s));
+        }
+    }
+    StepCtx c;
+    // rank 1: the joint group norm of every summed factor is folded as at world size 1 (no
+    // k_orth_reg launch): k_xchg leaves per-item sums of squares and a raw copy (history slot 2)
+    // that the next iteration's kernels normalise on the fly
+    const bool nfold = c.fuse = p->rbucket == 1;
+    c.raw_slot = 2;
+    // ranks 2/4, two iterations (every step starts even): the Q orthonormalisation from the
+    // exchange's Gram partials of the summed Q (k_orth_chain instead of k_orth_chol)
+    const bool gfold = c.xgram = p->qfold_ok && p->iters == 2 && p->even(step, 0);
+    c.fl = fold ? &fa : nullptr;
+    for (int it = 0; it < p->iters; ++it) {
+        c.xout = p->xslot(step, it);
+        if (int st = compress_impl(p, grads, step, it, s, c)) return st;
+        const bool e = p->even(step, it);
+        XchgArgs xa{};
+        const bool ss_out = nfold && it + 1 < p->iters;
+        const bool gram = gfold && it == 0;  // even: the Q side; k_orth_chain of iteration 1 reads the Gram
+        if (ss_out || gram) {  // per reduction item of the summed factor, and its raw copy
+            xa.items = p->dev(e ? p->red_even : p->red_odd);
+            xa.nitems = int32_t(e ? p->red_even.size() : p->red_odd.size());
+            xa.mats = p->dev(p->mats);
+            xa.even = e ? 1 : 0;
+            xa.dst2 = p->hist(2, it);
+            if (ss_out) xa.ss_out = p->dev<float>(p->o_ss) + size_t(it & 1) * p->ss_stride;
+            if (gram) xa.gram = p->dev<double>(p->o_gram);
+            if (gram) xa.gram_r = p->rbucket;
+        }
+        xa.peers = reinterpret_cast<const char* const*>(p->dev(p->ipc_peer));
+        xa.own_flag = reinterpret_cast<uint64_t*>(p->ipc_buf) + it;
+        xa.flag_off = int64_t(it) * int64_t(sizeof(uint64_t));
+        xa.slot_off = p->xslot_off(step, it);
+        xa.dst = e ? p->Q : p->P;
+        xa.n = e ? p->qtot : p->ptot;
+        const bool tail = it == last && has_flat;
+        if (tail) {
+            xa.flat_dst = mix ? nullptr : static_cast<float*>(flat_out);
+            xa.flat_off = p->ipc_flat_off;
+            xa.nflat = f->total;
+        }
+        xa.epoch = uint64_t(step) + 1;
+        xa.nonces = p->dev(p->ipc_nonces);
+        xa.own_nonce = p->ipc_nonce;
+        xa.spin_limit = spin;
+        xa.world = world;
+        xa.rank = p->ipc_rank;
+        xa.err = p->xerr_dev;
+        xa.err_dev = reinterpret_cast<int32_t*>(static_cast<char*>(p->ipc_buf) + kXchgErrOff);
+        if (tail && mix) {  // the summed flat tail goes out as bf16 (the last iteration never takes the item form)
+            XchgMixArgs xm{};
+            xm.entries = fa.entries;
+            xm.items = fa.items;
+            xm.nitems = fa.nitems;
+            xm.flat_out = dst ? nullptr : flat_out;
+            xm.unc_dst = dst ? dst->unc_dst : nullptr;
+            PSGD_HIP(launch_xchg_mix(xa, xm, dst != nullptr, s));
+        } else {
+            PSGD_HIP(launch_xchg(xa, s));
+        }
+    }
+    // the output pass: the route and the term sources are the same with and without `mix` (fuse and
+    // write_out clear: the earlier iterations' summed factors in history slot 2, where the item form
+    // of k_xchg or k_orth's save left them); no flat items ride in it
+    return decompress_impl(p, grads, out, step, world, s, mix ? comm_out_ctx(mix, dst) : StepCtx{});
+}
+
 extern "C" {
 
 int psgd_ipc_handle_bytes(int64_t* bytes) {
@@ -298,22 +407,11 @@ int psgd_ipc_status(psgd_plan* p, int32_t* timed_out) {
     return PSGD_OK;
 }
 
-// World size W over the IPC exchange (include/psgd.h): per iteration the codec kernels (the
-// reduction or fused final pass also writes the local factor into this rank's exchange slot),
-// then k_xchg (flag, bounded wait for the peers' flags, rank-order SUM into the state buffer; the
-// last one also sums the uncompressed tensors packed /W into flat_out), then the output pass.
-// Nothing leaves the stream: no host barrier, no host synchronisation.
 int psgd_aggregate_ipc(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
                        void* flat_out, void* stream) {
     if (!p || !grads || !out) return fail(PSGD_ERR_VALUE, "null argument");
     if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (p->ipc_peer.empty()) return fail(PSGD_ERR_STATE, "psgd_ipc_open first");
-    // a wait of an earlier step gave up: that step's sums were invalid and the two-parity slot
-    // reuse is no longer safe, so every later step is refused (the ranks have drifted apart)
-    if (p->xerr_set())
-        return fail(PSGD_ERR_STATE, "an earlier IPC exchange wait timed out (a peer did not arrive within "
-                                    "PSGD_IPC_SPIN); the exchange is invalid until psgd_ipc_close");
-    if (step < 0 || step >= 0xffffffffLL) return fail(PSGD_ERR_VALUE, "step out of range (epochs are 32-bit)");
+    if (int st = ipc_check(p, step)) return st;
     if (int st = check_out(out)) return st;
     const bool has_flat = f && f->total > 0;
     if (has_flat) {
@@ -323,68 +421,8 @@ int psgd_aggregate_ipc(psgd_plan* p, void* const* grads, void* out, int64_t step
         if (f->total > p->ipc_flat_cap) return fail(PSGD_ERR_VALUE, "flat tensors exceed the exchange buffer (psgd_ipc_create)");
     }
     DevScope scope(p->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int world = p->ipc_world;
-    const int last = p->iters - 1;
-    static const uint32_t spin = uint32_t(std::min<int64_t>(env_int("PSGD_IPC_SPIN", int64_t(1) << 26), 0xffffffffLL));
-    // x / W into this rank's last slot: inside the first even product's launch when the step
-    // starts even, else its own launch
-    FlatArgs fa{};
-    const bool fold = has_flat && p->even(step, 0);
-    float* flat_slot = p->xslot(step, last) + p->ipc_flat_off;
-    if (has_flat) {
-        if (int st = flat_args(f, unc, flat_slot, world, s, &fa)) return st;
-        if (!fold) PSGD_HIP(launch_flat_pack(f->dtype, fa, s));
-    }
-    StepCtx c;
-    // rank 1: the joint group norm of every summed factor is folded as at world size 1 (no
-    // k_orth_reg launch): k_xchg leaves per-item sums of squares and a raw copy (history slot 2)
-    // that the next iteration's kernels normalise on the fly
-    const bool nfold = c.fuse = p->rbucket == 1;
-    c.raw_slot = 2;
-    // ranks 2/4, two iterations (every step starts even): the Q orthonormalisation from the
-    // exchange's Gram partials of the summed Q (k_orth_chain instead of k_orth_chol)
-    const bool gfold = c.xgram = p->qfold_ok && p->iters == 2 && p->even(step, 0);
-    c.fl = fold ? &fa : nullptr;
-    for (int it = 0; it < p->iters; ++it) {
-        c.xout = p->xslot(step, it);
-        if (int st = compress_impl(p, grads, step, it, s, c)) return st;
-        const bool e = p->even(step, it);
-        XchgArgs xa{};
-        const bool ss_out = nfold && it + 1 < p->iters;
-        const bool gram = gfold && it == 0;  // even: the Q side; k_orth_chain of iteration 1 reads the Gram
-        if (ss_out || gram) {  // per reduction item of the summed factor, and its raw copy
-            xa.items = p->dev(e ? p->red_even : p->red_odd);
-            xa.nitems = int32_t(e ? p->red_even.size() : p->red_odd.size());
-            xa.mats = p->dev(p->mats);
-            xa.even = e ? 1 : 0;
-            xa.dst2 = p->hist(2, it);
-            if (ss_out) xa.ss_out = p->dev<float>(p->o_ss) + size_t(it & 1) * p->ss_stride;
-            if (gram) xa.gram = p->dev<double>(p->o_gram);
-            if (gram) xa.gram_r = p->rbucket;
-        }
-        xa.peers = reinterpret_cast<const char* const*>(p->dev(p->ipc_peer));
-        xa.own_flag = reinterpret_cast<uint64_t*>(p->ipc_buf) + it;
-        xa.flag_off = int64_t(it) * int64_t(sizeof(uint64_t));
-        xa.slot_off = p->xslot_off(step, it);
-        xa.dst = e ? p->Q : p->P;
-        xa.n = e ? p->qtot : p->ptot;
-        if (it == last && has_flat) {
-            xa.flat_dst = static_cast<float*>(flat_out);
-            xa.flat_off = p->ipc_flat_off;
-            xa.nflat = f->total;
-        }
-        xa.epoch = uint64_t(step) + 1;
-        xa.nonces = p->dev(p->ipc_nonces);
-        xa.own_nonce = p->ipc_nonce;
-        xa.spin_limit = spin;
-        xa.world = world;
-        xa.rank = p->ipc_rank;
-        xa.err = p->xerr_dev;
-        xa.err_dev = reinterpret_cast<int32_t*>(static_cast<char*>(p->ipc_buf) + kXchgErrOff);
-        PSGD_HIP(launch_xchg(xa, s));
-    }
-    return decompress_impl(p, grads, out, step, world, s, StepCtx{});
+    return aggregate_ipc_ctx(p, grads, out, step, has_flat ? f : nullptr, unc, flat_out, static_cast<hipStream_t>(stream),
+                             nullptr, nullptr);
 }
 
 }  // extern "C"

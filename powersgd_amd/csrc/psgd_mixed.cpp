@@ -21,6 +21,10 @@
 // The residual already holds residual + gradients (the hook adds each bucket on arrival), so the
 // call is psgd_aggregate_comm on the residual and the GATHER alone, and the final pass stores each
 // tensor's bf16 average at the tensor's own destination (MixDst): no ADD, no dense output.
+// psgd_aggregate_mixed_ipc / psgd_aggregate_mixed_ipc_dst: the same two forms over the plan's IPC
+// exchange session (psgd_aggregate_ipc on the residual between the ADD and the GATHER). Admission is
+// the communicator forms' (the output pass takes the same route); the flat tail needs no staging:
+// it is packed into the exchange slot and the last exchange stores its sums as bf16 (k_xchg_mix).
 #include <memory>
 #include <string>
 
@@ -314,6 +318,60 @@ int mixed_dst_impl(psgd_plan* p, void* const* residual, void* const* dst, int64_
     return aggregate_comm_ctx(p, residual, nullptr, step, f, unc_residual, nullptr, comm, s, &x, &t);
 }
 
+// psgd_aggregate_mixed_ipc / psgd_aggregate_mixed_ipc_dst past their argument checks: the
+// session's state, then admission for the session's world size (the output pass of the IPC step
+// takes the communicator step's route: the same instances, the same admission), then the pointer
+// tables. Everything that can refuse comes before the ADD. No staging buffer: the flat tail lives
+// in the exchange slot and k_xchg_mix stores its sums as bf16
+int mixed_ipc_impl(psgd_plan* p, void* const* grads, void* const* residual, void* out, int64_t step, psgd_flat* f,
+                   void* const* unc, void* const* unc_residual, void* flat_out, hipStream_t s) {
+    if (int st = ipc_check(p, step)) return st;
+    if (f && f->total > p->ipc_flat_cap)
+        return fail(PSGD_ERR_VALUE, "flat tensors exceed the exchange buffer (psgd_ipc_create)");
+    DevScope scope(p->device);
+    if (int st = ensure(p)) return st;
+    psgd_plan::Mixed& m = *p->mixed;
+    // the tiling the step will run on (the residual's alignment decides the vector layout)
+    if (int st = refresh_pointers(p, residual, s)) return st;
+    admit_comm(p);
+    if (!comm_eligible(p, p->ipc_world))
+        return fail(PSGD_ERR_VALUE, "psgd_aggregate_mixed_ipc: no admitted bf16-output instance of this plan's final "
+                                    "pass (two waves per SIMD, no scratch)");
+    MixArgs x{};
+    if (f) {
+        if (int st = unc_table(m, f, unc, unc_residual, s)) return st;
+        PSGD_HIP(m.unc_tab.select(unc, s));
+        x.unc_src = m.unc_tab.table();
+    }
+    if (int st = psgd_runs_add_list(m.add, grads, residual, 1, s)) return st;
+    return aggregate_ipc_ctx(p, residual, out, step, f, unc_residual, flat_out, s, &x, nullptr);
+}
+
+int mixed_ipc_dst_impl(psgd_plan* p, void* const* residual, void* const* dst, int64_t step, psgd_flat* f,
+                       void* const* unc_residual, void* const* unc_dst, hipStream_t s) {
+    if (int st = ipc_check(p, step)) return st;
+    if (f && f->total > p->ipc_flat_cap)
+        return fail(PSGD_ERR_VALUE, "flat tensors exceed the exchange buffer (psgd_ipc_create)");
+    DevScope scope(p->device);
+    if (int st = ensure(p)) return st;
+    psgd_plan::Mixed& m = *p->mixed;
+    if (int st = refresh_pointers(p, residual, s)) return st;
+    admit_dst(p);
+    if (!dst_eligible(p, p->ipc_world))
+        return fail(PSGD_ERR_VALUE, "psgd_aggregate_mixed_ipc_dst: no admitted destination-table instance of this "
+                                    "plan's final pass (two waves per SIMD, no scratch)");
+    MixArgs x{};
+    MixDst t{};
+    if (f) {
+        if (int st = unc_table(m, f, unc_dst, unc_residual, s)) return st;
+        PSGD_HIP(m.unc_dst.select(unc_dst, s));
+        t.unc_dst = m.unc_dst.table();
+    }
+    PSGD_HIP(m.dst.select(dst, s));
+    t.dst = m.dst.table();
+    return aggregate_ipc_ctx(p, residual, nullptr, step, f, unc_residual, nullptr, s, &x, &t);
+}
+
 }  // namespace
 
 void psgd::mixed_release(psgd_plan* p) {
@@ -423,6 +481,42 @@ int psgd_aggregate_mixed_comm_dst(psgd_plan* p, void* const* residual, void* con
                                   static_cast<hipStream_t>(stream), &refused);
     if (st && !refused) comm_poison(comm, psgd_last_error());
     return st;
+}
+
+int psgd_aggregate_mixed_ipc(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,
+                             psgd_flat* f, void* const* unc_bf16, void* const* unc_residual, void* flat_out_bf16,
+                             void* stream) {
+    // the argument errors (null, a negative step) before the plan's state
+    if (!p || !grads_bf16 || !residual || !out_bf16) return fail(PSGD_ERR_VALUE, "null argument");
+    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
+    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
+    if (int st = check_out(out_bf16)) return st;
+    const bool has_flat = f && f->total > 0;
+    if (has_flat)
+        if (int st = check_flat(f, unc_bf16 && unc_residual && flat_out_bf16, f->dtype == PSGD_F32 && f->device == p->device,
+                                PSGD_ERR_VALUE, "psgd_aggregate_mixed_ipc takes an fp32 flat plan (the uncompressed tensors' "
+                                                "residual) on the codec's device"))
+            return st;
+    if (int st = check_tensors(p, grads_bf16, residual)) return st;
+    return mixed_ipc_impl(p, grads_bf16, residual, out_bf16, step, has_flat ? f : nullptr, unc_bf16, unc_residual,
+                          flat_out_bf16, static_cast<hipStream_t>(stream));
+}
+
+int psgd_aggregate_mixed_ipc_dst(psgd_plan* p, void* const* residual, void* const* dst_bf16, int64_t step, psgd_flat* f,
+                                 void* const* unc_residual, void* const* unc_dst_bf16, void* stream) {
+    if (!p || !residual || !dst_bf16) return fail(PSGD_ERR_VALUE, "null argument");
+    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
+    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
+    const bool has_flat = f && f->total > 0;
+    if (has_flat)
+        if (int st = check_flat(f, unc_residual && unc_dst_bf16, f->dtype == PSGD_F32 && f->device == p->device,
+                                PSGD_ERR_VALUE, "psgd_aggregate_mixed_ipc_dst takes an fp32 flat plan (the uncompressed "
+                                                "tensors' residual) on the codec's device"))
+            return st;
+    // eligibility, then every tensor's two pointers: the destinations are bf16 like the gradients
+    if (int st = check_tensors(p, dst_bf16, residual)) return st;
+    return mixed_ipc_dst_impl(p, residual, dst_bf16, step, has_flat ? f : nullptr, unc_residual, unc_dst_bf16,
+                              static_cast<hipStream_t>(stream));
 }
 
 int psgd_aggregate_mixed(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,

@@ -590,6 +590,14 @@ int decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t step, i
 int flat_args(psgd_flat* f, void* const* tensors, void* flat, int32_t world, hipStream_t s, FlatArgs* out);
 // psgd_ipc.cpp: the plan's exchange region goes back to the process's arena
 void ipc_release(psgd_plan* p);
+// psgd_ipc.cpp: what a step over the exchange needs of the session, checked before anything is
+// launched: open, no timed-out wait pending, a 32-bit epoch
+int ipc_check(const psgd_plan* p, int64_t step);
+// psgd_ipc.cpp: the world-size-W step of psgd_aggregate_ipc; with `mix`, of psgd_aggregate_mixed_ipc
+// (`grads` the fp32 residual, `out` / `flat_out` bf16, `unc` the uncompressed tensors' fp32
+// residual); with `mix` and `dst`, of psgd_aggregate_mixed_ipc_dst (`out` and `flat_out` unused)
+int aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
+                      void* flat_out, hipStream_t s, const MixArgs* mix, const MixDst* dst);
 // psgd_mixed.cpp: frees the plan's mixed state
 void mixed_release(psgd_plan* p);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`

@@ -72,12 +72,13 @@ class PowerSGDState:
     of 2.
 
     ``fused=True`` (bfloat16 parameters with ``residual_dtype=torch.float32`` only) completes an
-    iteration in ONE library call wherever it applies (psgd_aggregate_mixed_comm_dst, include/
-    psgd.h): the codec's final pass stores the bf16 rounding of each parameter's average straight
-    into that parameter's view of its DDP bucket, so no fp32 output slab is written and no
-    per-bucket gather runs. Bit for bit the three stages it replaces. It applies on a compressing
-    step, in a process group that runs over the library's own communicator (not ``PSGD_COMM=ipc`` /
-    ``torch``, not gloo), on a plan the call serves (rank bucket 1 / 2 / 4); every other
+    iteration in ONE library call wherever it applies (psgd_aggregate_mixed_comm_dst, or
+    psgd_aggregate_mixed_ipc_dst under ``PSGD_COMM=ipc``; include/psgd.h): the codec's final pass
+    stores the bf16 rounding of each parameter's average straight into that parameter's view of its
+    DDP bucket, so no fp32 output slab is written and no per-bucket gather runs. Bit for bit the
+    three stages it replaces. It applies on a compressing step, in a process group that runs over
+    the library's own communicator or over the IPC exchange (not ``PSGD_COMM=torch``, not gloo
+    without the IPC exchange), on a plan the call serves (rank bucket 1 / 2 / 4); every other
     completion runs the three stages (``fused_folds()`` tells which)."""
 
     fused = False  # (class default: the three-stage completion)
@@ -227,17 +228,26 @@ class PowerSGDState:
             return None
         return codec._rccl_comm()
 
+    def _fused_ipc(self) -> bool:
+        """This process group runs over the codec's IPC exchange (``PSGD_COMM=ipc``)."""
+        return is_distributed() and self.powersgd._powersgd._ipc_mode()
+
     def _fused_applies(self) -> bool:
-        """The completion about to run compresses, over the library's communicator, on a plan
-        psgd_aggregate_mixed_comm_dst serves (both step parities: a plan is eligible as a whole)."""
+        """The completion about to run compresses, over the library's communicator or the IPC
+        exchange, on a plan psgd_aggregate_mixed_comm_dst / psgd_aggregate_mixed_ipc_dst serves (both
+        step parities: a plan is eligible as a whole)."""
         inner = self.powersgd
         if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
             return False
-        comm = self._fused_comm()
-        if comm is None:
-            return False
+        if self._fused_ipc():
+            world = dist.get_world_size()
+        else:
+            comm = self._fused_comm()
+            if comm is None:
+                return False
+            world = comm.world
         plan = inner._powersgd._plan
-        return plan.mixed_folds_dst(0, comm.world) == 1 and plan.mixed_folds_dst(1, comm.world) == 1
+        return plan.mixed_folds_dst(0, world) == 1 and plan.mixed_folds_dst(1, world) == 1
 
     def fused_folds(self):
         """``(fold_in, fold_out)`` of the NEXT completion: ``(0, 1)`` when it takes the one-call form
@@ -261,8 +271,15 @@ class PowerSGDState:
         if inner._unc is not None:
             kw = dict(flat=inner._unc.plan, unc_residual=inner._table.unc_addr(),
                       unc_dst_bf16=self._dst_table.unc_addr())
-        codec._plan.aggregate_mixed_comm_dst(inner._table.comp_addr(), self._dst_table.comp_addr(), codec.step_counter,
-                                             self._fused_comm(), _stream(self.residual.device), **kw)
+        if self._fused_ipc():
+            # collective, once: exactly as PowerSGD.aggregate sets the exchange up
+            codec._ipc_setup(inner._unc.numel if inner._unc is not None else 0)
+            codec._plan.aggregate_mixed_ipc_dst(inner._table.comp_addr(), self._dst_table.comp_addr(),
+                                                codec.step_counter, _stream(self.residual.device), **kw)
+        else:
+            codec._plan.aggregate_mixed_comm_dst(inner._table.comp_addr(), self._dst_table.comp_addr(),
+                                                 codec.step_counter, self._fused_comm(), _stream(self.residual.device),
+                                                 **kw)
         codec.step_counter += 1
         pending, self._pending = self._pending, []
         self._seen = [False] * len(self.params)

@@ -23,8 +23,10 @@ pass stores the bf16 averages itself (no GATHER pass), and where a step is one g
 other steps the library launches the ADD). In a process group that runs over the library's own RCCL
 communicator the one call is psgd_aggregate_mixed_comm: the output fold on every step, the ADD
 always a launch of the library's, the uncompressed tensors all-reduced in fp32 and rounded in the
-final launch. Bit for bit the three-stage flow above; every other case (``PSGD_COMM=ipc`` /
-``torch``, gloo, an ineligible plan) runs it.
+final launch. With ``PSGD_COMM=ipc`` it is psgd_aggregate_mixed_ipc over the codec's IPC exchange
+session: the same output fold, and the last exchange stores the uncompressed tensors' averages as
+bf16 itself. Bit for bit the three-stage flow above; every other case (``PSGD_COMM=torch``, gloo
+without the IPC exchange, an ineligible plan) runs it.
 """
 from __future__ import annotations
 
@@ -110,32 +112,43 @@ class Fp32ResidualPowerSGD(Aggregator):
             return None
         return codec._rccl_comm()
 
+    def _fused_world(self):
+        """The world size the communicator-route admission is asked for (psgd_plan_mixed_folds_comm):
+        the process group's under ``PSGD_COMM=ipc`` (the exchange session spans it), the library
+        communicator's over RCCL, None on every other transport."""
+        if self.inner._powersgd._ipc_mode():
+            return torch.distributed.get_world_size()
+        comm = self._fused_comm()
+        return None if comm is None else comm.world
+
     def _fused_applies(self) -> bool:
         """The step about to run compresses, on a plan the one-call form serves (both step parities:
         a plan is eligible or not as a whole): psgd_aggregate_mixed in one process,
-        psgd_aggregate_mixed_comm in a process group that runs over the library's communicator."""
+        psgd_aggregate_mixed_comm in a process group that runs over the library's communicator,
+        psgd_aggregate_mixed_ipc in one that runs over the IPC exchange."""
         inner = self.inner
         if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
             return False
         plan = inner._powersgd._plan
         if is_distributed():
-            comm = self._fused_comm()
-            if comm is None:
+            world = self._fused_world()
+            if world is None:
                 return False
-            return plan.mixed_folds_comm(0, comm.world)[1] == 1 and plan.mixed_folds_comm(1, comm.world)[1] == 1
+            return plan.mixed_folds_comm(0, world)[1] == 1 and plan.mixed_folds_comm(1, world)[1] == 1
         return plan.mixed_folds(0)[1] == 1 and plan.mixed_folds(1)[1] == 1
 
     def fused_folds(self):
         """``(fold_in, fold_out)`` of the NEXT ``aggregate`` call: 1 where the ingest of the bf16
         gradients / the bf16 rounding of the averages will run inside the codec's own gradient
-        pass (psgd_plan_mixed_folds; over a communicator psgd_plan_mixed_folds_comm: ``(0, 1)``);
+        pass (psgd_plan_mixed_folds; over a communicator or the IPC exchange
+        psgd_plan_mixed_folds_comm: ``(0, 1)``);
         ``(0, 0)`` whenever that call runs the three-stage flow (``fused=False``, a warm-up step, a
         process group on another transport, a plan the fused call refuses)."""
         if not (self.fused and self._fused_applies()):
             return (0, 0)
         codec = self.inner._powersgd
         if is_distributed():
-            return codec._plan.mixed_folds_comm(codec.step_counter, self._fused_comm().world)
+            return codec._plan.mixed_folds_comm(codec.step_counter, self._fused_world())
         return codec._plan.mixed_folds(codec.step_counter)
 
     def _aggregate_fused(self, gradients: List[torch.Tensor], stream: int) -> List[torch.Tensor]:
@@ -158,6 +171,9 @@ class Fp32ResidualPowerSGD(Aggregator):
         inner._table.fill(self.views)
         inner.step_counter += 1
         outs = st["comp_slab"].get()
+        ipc = is_distributed() and codec._ipc_mode()
+        if ipc:  # collective, once: exactly as PowerSGD.aggregate sets the exchange up
+            codec._ipc_setup(inner._unc.numel if inner._unc is not None else 0)
         comm = self._fused_comm()
         kw = {}
         if inner._unc is not None:
@@ -165,7 +181,10 @@ class Fp32ResidualPowerSGD(Aggregator):
             kw = dict(flat=inner._unc.plan, unc_bf16=st["grads"].unc_addr(), unc_residual=inner._table.unc_addr(),
                       flat_out=st["unc_slab"].data_ptr())
             outs = outs + unc
-        if comm is not None:
+        if ipc:
+            codec._plan.aggregate_mixed_ipc(st["grads"].comp_addr(), inner._table.comp_addr(),
+                                            st["comp_slab"].data_ptr(), codec.step_counter, stream, **kw)
+        elif comm is not None:
             codec._plan.aggregate_mixed_comm(st["grads"].comp_addr(), inner._table.comp_addr(),
                                              st["comp_slab"].data_ptr(), codec.step_counter, comm, stream, **kw)
         else:

@@ -519,6 +519,46 @@ int psgd_aggregate_mixed_ipc_dst(psgd_plan* plan, void* const* residual, void* c
                                  int64_t step, psgd_flat* flat, void* const* unc_residual,
                                  void* const* unc_dst_bf16, void* stream);
 
+/* ------------- the default (fp32) DDP hook's one-call completion: fp32 destinations ------------ */
+/* psgd_aggregate_comm and psgd_aggregate_ipc with every average stored at its tensor's own
+ * destination (the tensor's gradient view inside a DDP bucket) instead of an output slab that a
+ * per-bucket psgd_runs_gather then copies. Each is DEFINED as a sequence of existing calls and
+ * equal to it bit for bit, with nothing else observable.
+ * psgd_aggregate_comm_dst:
+ *   1. psgd_aggregate_comm(plan, grads, out, step, flat, unc, flat_out, comm): the same kernels in
+ *      the same order, the same collectives (order and count), residual and P/Q state
+ *   2. dst[i][e] = out_i[e], unc_dst[k][e] = flat_k[e]
+ * psgd_aggregate_ipc_dst: the same with psgd_aggregate_ipc (the same exchanges, flags and epochs).
+ * dst is in the plan's tensor order, unc_dst in the flat plan's. Each pointer is 4-byte aligned or
+ * better and addresses numel dense fp32 elements; nothing outside those numel elements is
+ * written. They are written, never accumulated into.
+ * Where the stages run: the final pass of the sequence (k_apply with two term sets; k_apply's
+ * world-size-1 form for one rank; k_lowrank_out after a fused k_final_odd; the VALU tiles at rank
+ * buckets 1-8, the matrix-core tiles at 16 and 32) is its destination-table instance. Its tiles,
+ * loads and arithmetic are laid out from the gradients' alignment and the plan's offsets exactly
+ * as in step 1; only the output store follows the destination: a vector tile whose first
+ * destination element is 16-byte aligned stores 16 bytes, any other four 4-byte elements, chosen
+ * once per tile; every store goes through a descriptor that spans the tile's rows of its own
+ * tensor. The flat tail is packed into a staging buffer of the plan's own (flat->total floats)
+ * where psgd_aggregate_comm / _ipc pack into flat_out, summed there by the collective / the last
+ * exchange, and copied to unc_dst by the leading workgroups of the final launch.
+ * Eligible: a bound PSGD_F32 plan, not wide (rank buckets 1-32), one bucket, with EVERY
+ * destination-table instance its routes name admitted (at least two waves per SIMD, no scratch;
+ * both step parities, one rank and W > 1). psgd_plan_dst_ok: *ok = 1 for such a plan, else 0: a
+ * property of the plan (step >= 0 and world >= 1 are validated only).
+ * Refusals: a non-fp32 plan PSGD_ERR_DTYPE; a wide plan, more than one bucket, an instance that
+ * is not admitted, a null pointer, a flat plan that is not fp32 on the codec's device, flat->total
+ * above the session's flat_numel: PSGD_ERR_VALUE; a destination that is not 4-byte aligned:
+ * PSGD_ERR_LAYOUT; an unbound plan, a poisoned communicator, no open session or a timed-out wait:
+ * PSGD_ERR_STATE. Every refusal comes before any launch, collective or exchange: gradients,
+ * destinations and P/Q state stay as they were, and the communicator / session stays usable. */
+int psgd_aggregate_comm_dst(psgd_plan* plan, void* const* grads, void* const* dst, int64_t step,
+                            psgd_flat* flat, void* const* unc, void* const* unc_dst, psgd_comm* comm,
+                            void* stream);
+int psgd_aggregate_ipc_dst(psgd_plan* plan, void* const* grads, void* const* dst, int64_t step,
+                           psgd_flat* flat, void* const* unc, void* const* unc_dst, void* stream);
+int psgd_plan_dst_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,9 @@ _SIGNATURES = {
     "psgd_plan_mixed_folds_dst": ([_vp, _i64, _i32, _P_i32], _i32),
     "psgd_aggregate_mixed_ipc": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_aggregate_mixed_ipc_dst": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
+    "psgd_aggregate_comm_dst": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_aggregate_ipc_dst": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_dst_ok": ([_vp, _i64, _i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -275,6 +278,27 @@ class Plan:
         check(lib().psgd_aggregate_mixed_comm_dst(self._h, residual, dst_bf16, step,
                                                   flat._h if flat is not None else None, unc_residual, unc_dst_bf16,
                                                   comm._h if comm is not None else None, stream))
+
+    # --- the fp32 averages stored at per-tensor destinations (the default DDP hook's one-call completion)
+    def dst_ok(self, step: int, world: int) -> int:
+        """1 where ``aggregate_comm_dst`` / ``aggregate_ipc_dst`` serve this plan (psgd_plan_dst_ok: a
+        property of the plan; ``step`` and ``world`` are validated only), 0 for a plan they refuse."""
+        ok = _i32()
+        check(lib().psgd_plan_dst_ok(self._h, step, world, ctypes.byref(ok)))
+        return int(ok.value)
+
+    def aggregate_comm_dst(self, grads, dst, step: int, comm: "Comm", stream: int, flat=None, unc=None,
+                           unc_dst=None) -> None:
+        """psgd_aggregate_comm_dst: ``aggregate_comm`` with every fp32 average stored at ``dst[i]`` /
+        ``unc_dst[k]`` by the final pass (no output slab). Raises for a plan it does not serve, before
+        anything is launched or any collective issued."""
+        check(lib().psgd_aggregate_comm_dst(self._h, grads, dst, step, flat._h if flat is not None else None, unc,
+                                            unc_dst, comm._h if comm is not None else None, stream))
+
+    def aggregate_ipc_dst(self, grads, dst, step: int, stream: int, flat=None, unc=None, unc_dst=None) -> None:
+        """psgd_aggregate_ipc_dst: the same over the plan's open exchange session (``aggregate_ipc``)."""
+        check(lib().psgd_aggregate_ipc_dst(self._h, grads, dst, step, flat._h if flat is not None else None, unc,
+                                           unc_dst, stream))
 
     # --- buckets of shape groups (W > 1 comm/compute overlap)
     def set_buckets(self, group_end: Sequence[int]) -> None:

@@ -652,7 +652,8 @@ __global__ __launch_bounds__(FinNT<R>::value) __attribute__((amdgpu_waves_per_eu
 #endif
 constexpr int kLowrankUR = PSGD_LOWRANK_UR;
 // DST (psgd_aggregate_mixed_comm_dst, T = bf16_pin_t; kDstVec / kDstElem): the output goes to
-// a.odst[d.tensor], a tensor of any 2-byte alignment; the store form as in apply_tile (psgd_stream.cuh)
+// a.odst[d.tensor], a tensor of any 2-byte alignment; the store form as in apply_tile (psgd_stream.cuh).
+// T = float (psgd_aggregate_comm_dst): a tensor of any 4-byte alignment, st_vec_dstf's forms
 template <typename T, int R, int NI, int V, int DST = 0>
 __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t) {
     const TileGeom g = tile_geom<V>(d, t);
@@ -697,7 +698,8 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
                     for (int v = 0; v < V; ++v) o[v] = o[v] + alpha * dotr<R>(pa[u][k], ba[k][v]);
                 if (g.active && row < g.row_end) {
                     const uint32_t off = uint32_t((row - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(T));
-                    if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
+                    if constexpr (DST != 0 && std::is_same<T, float>::value) st_vec_dstf<DST>(rO, off, o);
+                    else if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
                     else st_vec<T>(rO, off, o);
                 }
             }
@@ -726,7 +728,8 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
         }
         if (g.active) {
             const uint32_t off = uint32_t((row - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(T));
-            if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
+            if constexpr (DST != 0 && std::is_same<T, float>::value) st_vec_dstf<DST>(rO, off, o);
+            else if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
             else st_vec<T>(rO, off, o);
         }
     }

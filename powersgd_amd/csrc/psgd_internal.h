@@ -516,6 +516,29 @@ hipError_t launch_lowrank_mix_dst(int R, int nterms, const ApplyArgs& a, const M
 hipError_t launch_apply_mix_dst(int R, int nterms, const ApplyArgs& a, int ntiles, hipStream_t s, int* waves);
 hipError_t launch_flat_round_dst(const FlatArgs& a, const MixArgs& x, void* const* unc_dst, hipStream_t s);
 
+// psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst (the default fp32 DDP hook's one-call form): the
+// final pass of an fp32 plan (rank buckets 1-32) stores each tensor's fp32 average at the tensor's
+// own destination (a view into a DDP bucket: dense, 4-byte aligned or better) instead of the
+// output slab. `dst` in the plan's tensor order (read as ApplyArgs::odst), `unc_dst` in the flat
+// plan's order; `stage` the plan-owned fp32 buffer the flat tail's collective (or last exchange)
+// summed into, in the flat plan's layout. The tiles are laid out exactly as the dense instances'
+// (from the gradients' alignment and the plan's offsets); only their output stores follow the
+// destination's alignment.
+struct DirectDst {
+    void* const* dst;
+    void* const* unc_dst;
+    float* stage;
+};
+// psgd_apply_dst.hip: the destination-table instances of k_apply<float> (shared: the 1-rank
+// communicator's; else two term sets) and of k_lowrank_out<float> (rank buckets 1 / 2). a.flat's
+// items are copy items (unc_dst[k] = stage) and come first. ntiles + items == 0: no launch;
+// `*waves` (if non-null) receives the resident waves per SIMD of the instance that would run, 0
+// when it uses scratch.
+hipError_t launch_apply_dst(int R, int nterms, bool shared, const ApplyArgs& a, const DirectDst& t, int ntiles,
+                            hipStream_t s, int* waves);
+hipError_t launch_lowrank_dst(int R, int nterms, const ApplyArgs& a, const DirectDst& t, int ntiles, hipStream_t s,
+                              int* waves);
+
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),
 // then two parities x iterations slots of xchg_slot floats each; the producer kernels (k_reduce,

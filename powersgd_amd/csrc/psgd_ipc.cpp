@@ -169,7 +169,8 @@ int psgd::ipc_check(const psgd_plan* p, int64_t step) {
 // gradients, so the flat tail is packed as without `mix`, and both stores follow dst's tables.
 // Every other launch, flag and epoch is the same in the three forms.
 int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
-                            void* flat_out, hipStream_t s, const MixArgs* mix, const MixDst* dst) {
+                            void* flat_out, hipStream_t s, const MixArgs* mix, const MixDst* dst,
+                            const DirectDst* fdst) {
     const bool has_flat = f != nullptr;
     const int world = p->ipc_world;
     const int last = p->iters - 1;
@@ -225,7 +226,7 @@ int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t
         xa.n = e ? p->qtot : p->ptot;
         const bool tail = it == last && has_flat;
         if (tail) {
-            xa.flat_dst = mix ? nullptr : static_cast<float*>(flat_out);
+            xa.flat_dst = mix ? nullptr : fdst ? fdst->stage : static_cast<float*>(flat_out);
             xa.flat_off = p->ipc_flat_off;
             xa.nflat = f->total;
         }
@@ -252,7 +253,13 @@ int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t
     // the output pass: the route and the term sources are the same with and without `mix` (fuse and
     // write_out clear: the earlier iterations' summed factors in history slot 2, where the item form
     // of k_xchg or k_orth's save left them); no flat items ride in it
-    return decompress_impl(p, grads, out, step, world, s, mix ? comm_out_ctx(mix, dst) : StepCtx{});
+    StepCtx d = mix ? comm_out_ctx(mix, dst) : StepCtx{};
+    if (fdst) {  // psgd_aggregate_ipc_dst: the last exchange summed the flat tail into fdst->stage; its
+                 // copy items ride in the output pass's destination-table instance
+        d.fdst = fdst;
+        d.fl = has_flat ? &fa : nullptr;
+    }
+    return decompress_impl(p, grads, out, step, world, s, d);
 }
 
 extern "C" {

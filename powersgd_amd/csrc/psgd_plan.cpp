@@ -47,6 +47,7 @@ psgd_plan::~psgd_plan() {
     }
     ipc_release(this);
     mixed_release(this);
+    direct_release(this);
     if (xerr_host) (void)hipHostFree(xerr_host);
     if (stamp_buf) (void)hipFree(stamp_buf);
 }

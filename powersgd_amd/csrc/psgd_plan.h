@@ -4,6 +4,7 @@
 //   psgd_step.cpp      step drivers (one stage function per IterRoute pass), the final-pass launch
 //                      functions shared with admission, and the reducer building blocks
 //   psgd_mixed.cpp     psgd_aggregate_mixed[_comm]: admission of the mixed instances, fold queries
+//   psgd_direct.cpp    psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst: admission, state, entry points
 //   psgd_ipc.cpp       the IPC exchange arena and psgd_aggregate_ipc
 //   psgd_flat.cpp      flat pack and DDP run tables
 //   psgd_comm.cpp      the communicator behind psgd_aggregate_comm
@@ -382,6 +383,23 @@ struct psgd_plan {
         TableCache dst, unc_dst;
     };
     Mixed* mixed = nullptr;
+    // psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst (psgd_direct.cpp): state of its own like
+    // Mixed, created by the first call or psgd_plan_dst_ok query; nothing of it lives in the
+    // caller's workspace. Admission of the fp32 destination-table instances of the output pass
+    // per communicator kind ([0]: world size > 1, [1]: one rank) and step parity under a key of
+    // its own; the destinations' pointer tables (change-detected: DDP rebuilds its buckets once);
+    // the fp32 staging of the flat tail (`flat->total` floats, grown by the first call that needs it)
+    struct Direct {
+        uint64_t key = ~uint64_t(0);
+        bool ok[2][2] = {};
+        char* dev = nullptr;
+        TableCache dst, unc_dst;
+        size_t unc_cap = 0;
+        char* unc_dev = nullptr;
+        float* stage = nullptr;
+        size_t stage_cap = 0;  // floats
+    };
+    Direct* direct = nullptr;
     int64_t xslot_off(int64_t step, int it) const {  // byte offset of a slot in every buffer
         return kXchgHeader + ((step & 1) * iters + it) * ipc_slot * int64_t(sizeof(float));
     }
@@ -501,6 +519,10 @@ struct StepCtx {
     // psgd_aggregate_mixed_comm_dst: the mixed output pass stores at these per-tensor destinations
     // (its destination-table instances) instead of `out`
     const MixDst* dst = nullptr;
+    // psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst: the plan's own fp32 output pass stores at
+    // these per-tensor destinations (psgd_apply_dst.hip) instead of `out`, and c.fl's items are
+    // copy items from the staged flat tail
+    const DirectDst* fdst = nullptr;
 };
 
 // The contexts of the two one-call steps, shared by the drivers and by admission (psgd_mixed.cpp):
@@ -569,6 +591,7 @@ struct OutRoute {
     bool timed;       // benchmark timing covers this launch
     bool flat;        // the context's flat items ride in the launch (k_lowrank_out takes none)
     bool dst;         // Mix / MixW / the mixed Lowrank: the destination-table instance (MixDst)
+    bool fdst;        // Plain: the fp32 destination-table instance (DirectDst)
     int reduced_slot; // history slot of the earlier iterations' reduced factors (1: never copied to 2)
 };
 
@@ -579,7 +602,7 @@ struct OutRoute {
 hipError_t launch_final_pass(const psgd_plan* p, const IterRoute& r, const FinalArgs& a, const MixArgs* mix, int ntiles,
                              hipStream_t s, int* waves);
 hipError_t launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArgs& a, const MixArgs* mix, int ntiles,
-                           hipStream_t s, int* waves, const MixDst* dst = nullptr);
+                           hipStream_t s, int* waves, const MixDst* dst = nullptr, const DirectDst* fdst = nullptr);
 
 // psgd_step.cpp
 int refresh_pointers(psgd_plan* p, void* const* grads, hipStream_t stream);
@@ -595,17 +618,23 @@ void ipc_release(psgd_plan* p);
 int ipc_check(const psgd_plan* p, int64_t step);
 // psgd_ipc.cpp: the world-size-W step of psgd_aggregate_ipc; with `mix`, of psgd_aggregate_mixed_ipc
 // (`grads` the fp32 residual, `out` / `flat_out` bf16, `unc` the uncompressed tensors' fp32
-// residual); with `mix` and `dst`, of psgd_aggregate_mixed_ipc_dst (`out` and `flat_out` unused)
+// residual); with `mix` and `dst`, of psgd_aggregate_mixed_ipc_dst (`out` and `flat_out` unused);
+// with `fdst` alone, of psgd_aggregate_ipc_dst (`out` and `flat_out` unused: fdst->stage)
 int aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
-                      void* flat_out, hipStream_t s, const MixArgs* mix, const MixDst* dst);
+                      void* flat_out, hipStream_t s, const MixArgs* mix, const MixDst* dst,
+                      const DirectDst* fdst = nullptr);
 // psgd_mixed.cpp: frees the plan's mixed state
 void mixed_release(psgd_plan* p);
+// psgd_direct.cpp: frees the plan's direct-store state
+void direct_release(psgd_plan* p);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
 int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
 // psgd_step.cpp: the world-size-W step of psgd_aggregate_comm; with `mix`, of psgd_aggregate_mixed_comm;
-// with `mix` and `dst`, of psgd_aggregate_mixed_comm_dst (`out` and `flat_out` unused)
+// with `mix` and `dst`, of psgd_aggregate_mixed_comm_dst (`out` and `flat_out` unused); with `fdst`
+// alone, of psgd_aggregate_comm_dst (`out` and `flat_out` unused: fdst->stage)
 int aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
-                       void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix, const MixDst* dst = nullptr);
+                       void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix, const MixDst* dst = nullptr,
+                       const DirectDst* fdst = nullptr);
 
 }  // namespace psgd
 
@@ -652,7 +681,8 @@ inline OutRoute psgd_plan::out_route(int64_t step, int world, const StepCtx& c) 
     o.shared = world == 1;
     o.out_nt = world == 1 ? out_nt : 0;
     o.timed = o.kind == OutRoute::Apply;
-    o.flat = o.kind == OutRoute::Apply || c.mix != nullptr;
+    o.fdst = c.mix == nullptr && c.fdst != nullptr;
+    o.flat = o.kind == OutRoute::Apply || c.mix != nullptr || o.fdst;
     o.dst = c.mix != nullptr && c.dst != nullptr;
     // fused (world size 1): the reduced factor was never copied to history slot 2
     o.reduced_slot = fused_norm(c.fuse, 1) ? 1 : 2;

@@ -511,9 +511,15 @@ hipError_t psgd::launch_final_pass(const psgd_plan* p, const IterRoute& r, const
 }
 
 hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArgs& a, const MixArgs* mix, int ntiles,
-                                 hipStream_t s, int* waves, const MixDst* dst) {
+                                 hipStream_t s, int* waves, const MixDst* dst, const DirectDst* fdst) {
     a.out_nt = o.out_nt;
     const int R = p->rbucket, I = p->iters;
+    if (o.fdst) {  // psgd_aggregate_comm_dst: the fp32 averages go to the per-tensor destinations
+        if (p->dtype != PSGD_F32) return hipErrorInvalidValue;
+        a.odst = fdst->dst;
+        if (o.kind == OutRoute::Lowrank) return launch_lowrank_dst(R, I, a, *fdst, ntiles, s, waves);
+        return launch_apply_dst(R, I, o.shared, a, *fdst, ntiles, s, waves);
+    }
     if (o.dst) {  // psgd_aggregate_mixed_comm_dst: the averages go to the per-tensor destinations
         a.odst = dst->dst;
         if (o.kind == OutRoute::Lowrank) return launch_lowrank_mix_dst(R, I, a, *mix, dst->unc_dst, ntiles, s, waves);
@@ -579,7 +585,7 @@ int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t s
     if (o.timed)
         if (int st = timing_begin(p, s, &ev, true)) return st;
     TimedScope ts(ev);
-    PSGD_HIP(launch_out_pass(p, o, aa, c.mix, nt, s, nullptr, c.dst));
+    PSGD_HIP(launch_out_pass(p, o, aa, c.mix, nt, s, nullptr, c.dst, c.fdst));
     return PSGD_OK;
 }
 
@@ -626,10 +632,14 @@ int refresh_table(psgd_plan* p, void* const* ptrs, TableCache& tab, hipStream_t 
 // `mix` and `dst` (psgd_aggregate_mixed_comm_dst): `grads` already holds residual + gradients, so
 // nothing is ingested: the flat tail is packed as psgd_aggregate_comm packs it (x / W, x = +0.0,
 // flat_pack_item<float>), with mix->stage as its flat buffer, and the round items store into
-// dst->unc_dst
+// dst->unc_dst.
+// `fdst` alone (psgd_aggregate_comm_dst): psgd_aggregate_comm's own sequence with fdst->stage where
+// `flat_out` goes (packed by the same kernels: inside the first even product's launch, else
+// flat_pack_item<float> in a launch of its own), the final pass's fp32 destination-table instance,
+// and copy items (fdst->unc_dst = stage) as its leading workgroups
 int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f,
                              void* const* unc, void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix,
-                             const MixDst* dst) {
+                             const MixDst* dst, const DirectDst* fdst) {
     const bool has_flat = f != nullptr;
     const int world = comm_world(comm);
     // x / W into the flat buffer, x = 0 (utils.py:43-47, powersgd.py:29-30): inside the first
@@ -637,7 +647,8 @@ int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_
     FlatArgs fa{};
     const bool ingest = mix && !dst;
     const bool fold = has_flat && !ingest && p->even(step, 0) && !p->wide();  // wide products carry no flat pack
-    if (fold || (mix && has_flat)) {
+    if (fdst) flat_out = fdst->stage;  // the collective's fp32 buffer; copy items follow it
+    if (fold || ((mix || fdst) && has_flat)) {
         if (int st = flat_args(f, unc, dst ? static_cast<void*>(mix->stage) : flat_out, world, s, &fa)) return st;
         if (ingest) PSGD_HIP(launch_flat_ingest(fa, *mix, s));
         else if (!fold) PSGD_HIP(launch_flat_pack(f->dtype, fa, s));
@@ -656,6 +667,10 @@ int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_
             return st;
     }
     StepCtx d = comm_out_ctx(mix, dst);
+    if (fdst) {  // the copy items ride in the final launch, whichever it is
+        d.fdst = fdst;
+        d.fl = has_flat ? &fa : nullptr;
+    }
     if (!mix) return decompress_impl(p, grads, out, step, world, s, d);
     // the round items ride in every final launch built for them; a 1-rank communicator's unfused
     // final pass is the world-size-1 instance, whose flat items ingest: the round follows it

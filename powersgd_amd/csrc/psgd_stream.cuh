@@ -129,6 +129,18 @@ struct StIo<float> {
     static __device__ __forceinline__ void st1(rsrc_t r, uint32_t off, float v) {
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, off, 0, AUX);
     }
+    // The fp32 destination-table instances (psgd_aggregate_comm_dst, psgd_apply_dst.hip) on a
+    // destination that is not 16-byte aligned (a tensor inside a DDP bucket is 4-byte aligned in
+    // general): the four values gathered into the 128-bit vector st4 hands to its store (the same
+    // sink for the arithmetic upstream), then four 4-byte stores
+    template <int AUX = PSGD_ST_AUX>
+    static __device__ __forceinline__ void st4e(rsrc_t r, uint32_t off, const float (&v)[4]) {
+        typedef unsigned v4u __attribute__((ext_vector_type(4)));
+        v4u x = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+        asm volatile("" : "+v"(x));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) __builtin_amdgcn_raw_buffer_store_b32(x[e], r, off + 4u * uint32_t(e), 0, AUX);
+    }
 };
 
 template <>
@@ -213,6 +225,19 @@ __device__ __forceinline__ void st_vec_dst(rsrc_t r, uint32_t off, const float (
 template <int DST, int AUX = PSGD_ST_AUX>
 __device__ __forceinline__ void st_vec_dst(rsrc_t r, uint32_t off, const float (&v)[1]) {
     StIo<bf16_pin_t>::template st1<AUX>(r, off, v[0]);
+}
+// The same for the fp32 destination-table instances (psgd_aggregate_comm_dst, TO = float, a
+// destination of any 4-byte alignment). kDstVec: the dense instance's 16-byte store; kDstElem: four
+// 4-byte stores, nt alone like the bf16 form's (partial lines merge in the L2 instead of leaving it
+// one by one). The kernel picks per tile with dst_al16.
+template <int DST, int AUX = PSGD_ST_AUX>
+__device__ __forceinline__ void st_vec_dstf(rsrc_t r, uint32_t off, const float (&v)[4]) {
+    if constexpr (DST == kDstElem) StIo<float>::template st4e<kStAuxOutNt>(r, off, v);
+    else StIo<float>::template st4<AUX>(r, off, v);
+}
+template <int DST, int AUX = PSGD_ST_AUX>
+__device__ __forceinline__ void st_vec_dstf(rsrc_t r, uint32_t off, const float (&v)[1]) {
+    StIo<float>::template st1<AUX>(r, off, v[0]);
 }
 
 template <typename T>
@@ -1194,7 +1219,9 @@ hipError_t dispatch_odd_mfma(int R, int nres, const ProductArgs& a, int ntiles, 
 // tensor of any 2-byte alignment (a view into a DDP bucket). The tile's layout (V, from the
 // residual's alignment and the plan's offsets), its loads and its arithmetic stay those of the
 // dense instance; only the store of a vector tile follows the destination (kDstVec / kDstElem,
-// picked per tile by the kernel with dst_al8).
+// picked per tile by the kernel with dst_al8). With TO = float (psgd_aggregate_comm_dst,
+// psgd_apply_dst.hip) the destination is 4-byte aligned or better and the forms are 16 bytes /
+// four 4-byte stores (st_vec_dstf, dst_al16).
 template <typename T, int R, int NI, bool SHARED, int V, bool ONT = false, typename TO = T, int DST = 0>
 __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t) {
     const TileGeom g = tile_geom<V>(d, t);
@@ -1299,7 +1326,9 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
             if (g.active && row + u * g.stride < g.row_end) {
                 const uint32_t eo = uint32_t((b.rc[u] - g.row_begin) * g.m + g.col0);
                 st_vec<T>(rD, eo * uint32_t(sizeof(T)), b.x[u]);
-                if constexpr (DST != 0)
+                if constexpr (DST != 0 && std::is_same<TO, float>::value)
+                    st_vec_dstf<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
+                else if constexpr (DST != 0)
                     st_vec_dst<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
                 else
                     st_vec<TO, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
@@ -1332,7 +1361,9 @@ struct ApplyMfmaLds {
     static constexpr int floats = kApplyMfmaSets * 64 * RP;
 };
 
-template <typename T, int R, bool SHARED, bool ONT>
+// DST (psgd_apply_dst.hip, T = float): the output goes to a.odst[d.tensor], 4-byte aligned or
+// better; kDstElem stores a row's quad as four 4-byte stores (the kernel picks per tile).
+template <typename T, int R, bool SHARED, bool ONT, int DST = 0>
 __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDesc& d, const Tile& t, float* qs) {
     constexpr int KQ = R / 4;
     constexpr int RP = ApplyMfmaLds<R>::RP;
@@ -1439,7 +1470,8 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
             }
             const uint32_t off = (rb + v) * rstride + cofs;
             st_vec<T>(rD, off, xo);
-            st_vec<T, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, oo);
+            if constexpr (DST != 0) st_vec_dstf<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, oo);
+            else st_vec<T, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, oo);
         }
     }
     __syncthreads();  // qs is staged again by the next tile of this workgroup (none today)

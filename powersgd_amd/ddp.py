@@ -79,9 +79,18 @@ class PowerSGDState:
     three stages it replaces. It applies on a compressing step, in a process group that runs over
     the library's own communicator or over the IPC exchange (not ``PSGD_COMM=torch``, not gloo
     without the IPC exchange), on a plan the call serves (rank bucket 1 / 2 / 4); every other
-    completion runs the three stages (``fused_folds()`` tells which)."""
+    completion runs the three stages (``fused_folds()`` tells which).
+
+    ``state.direct_store = True`` (float32 parameters with a float32 residual, ``fused=False``; set
+    before the first backward) is the same one-call completion for the default fp32 hook
+    (psgd_aggregate_comm_dst, or psgd_aggregate_ipc_dst under ``PSGD_COMM=ipc``): the final pass
+    stores each parameter's fp32 average straight into its view of its DDP bucket, at rank buckets
+    1 to 32. Bit for bit the three stages; ``direct_store_applies()`` tells whether the next
+    completion takes it (a compressing step, the library's communicator or the IPC exchange, a plan
+    ``Plan.dst_ok`` reports 1 for). Opt-in: the default is ``False``."""
 
     fused = False  # (class default: the three-stage completion)
+    _direct = False
 
     def __init__(self, config: Config, params, process_group=None, residual_dtype=None, fused=False):
         if process_group is not None and process_group is not dist.group.WORLD:
@@ -132,8 +141,9 @@ class PowerSGDState:
         self._seen = [False] * len(self.params)
         self._nseen = 0
         self._pending: List[tuple] = []
-        # fused: per parameter its gradient view inside the pending bucket (the destination of its
-        # average), and their native split by the compression mask (built by the first fused completion)
+        # fused / direct_store: per parameter its gradient view inside the pending bucket (the
+        # destination of its average), and their native split by the compression mask (built by the
+        # first one-call completion)
         self._dst: List[Optional[torch.Tensor]] = [None] * len(self.params)
         self._dst_table = None
 
@@ -161,7 +171,7 @@ class PowerSGDState:
             for i in idx:
                 self._seen[i] = True
                 self._nseen += 1
-            if self.fused:
+            if self.fused or self._direct:
                 for i, g in zip(idx, grads):
                     self._dst[i] = g.view(self.params[i].shape)
             self._pending.append((buf, runs, fut))
@@ -178,6 +188,21 @@ class PowerSGDState:
             self._fail(e, fut)
             raise
         return fut
+
+    @property
+    def direct_store(self) -> bool:
+        return self._direct
+
+    @direct_store.setter
+    def direct_store(self, on: bool) -> None:
+        on = bool(on)
+        if on and not (self.params[0].dtype == torch.float32 and self.residual.dtype == torch.float32
+                       and not self.fused):
+            raise ValueError(f"direct_store needs float32 parameters with a float32 residual and fused=False; got "
+                             f"{self.params[0].dtype} parameters, a {self.residual.dtype} residual, fused={self.fused}")
+        if on != self._direct and (self._pending or self.powersgd.step_counter > 0):
+            raise ValueError("direct_store is set before the first backward")
+        self._direct = on
 
     def _fail(self, err: Exception, fut: "torch.futures.Future") -> None:
         """Fail this iteration: every pending bucket future (and this one) gets the exception, so
@@ -288,10 +313,63 @@ class PowerSGDState:
         for buf, _, fut in pending:
             fut.set_result(buf)
 
+    def direct_store_applies(self) -> bool:
+        """The NEXT completion takes the one-call form of ``direct_store``: it is set, the step
+        compresses, the process group runs over the library's communicator or the IPC exchange, and
+        the plan is one psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst serve."""
+        if not self._direct:
+            return False
+        inner = self.powersgd
+        if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
+            return False
+        if self._fused_ipc():
+            world = dist.get_world_size()
+        else:
+            comm = self._fused_comm()
+            if comm is None:
+                return False
+            world = comm.world
+        plan = inner._powersgd._plan
+        return plan.dst_ok(0, world) == 1 and plan.dst_ok(1, world) == 1
+
+    def _complete_direct(self) -> None:
+        """``PowerSGD.aggregate`` of the codec on the residual views as one library call, as
+        ``_complete_fused``: the same bookkeeping, the fp32 averages stored by the final pass into the
+        pending buckets' gradient views. No ``_gather``, no output slab."""
+        inner, codec = self.powersgd, self.powersgd._powersgd
+        if self._dst_table is None:
+            self._dst_table = _psgd_host.PtrTable([list(v.shape) for v in self.views], inner.is_compressed_mask,
+                                                  _lib.PSGD_F32, self._dev_index)
+        self._dst_table.fill(self._dst)
+        inner.step_counter += 1
+        inner._table.fill(self.views)
+        kw = {}
+        if inner._unc is not None:
+            kw = dict(flat=inner._unc.plan, unc=inner._table.unc_addr(), unc_dst=self._dst_table.unc_addr())
+        if self._fused_ipc():
+            # collective, once: exactly as PowerSGD.aggregate sets the exchange up
+            codec._ipc_setup(inner._unc.numel if inner._unc is not None else 0)
+            codec._plan.aggregate_ipc_dst(inner._table.comp_addr(), self._dst_table.comp_addr(), codec.step_counter,
+                                          _stream(self.residual.device), **kw)
+        else:
+            codec._plan.aggregate_comm_dst(inner._table.comp_addr(), self._dst_table.comp_addr(), codec.step_counter,
+                                           self._fused_comm(), _stream(self.residual.device), **kw)
+        codec.step_counter += 1
+        pending, self._pending = self._pending, []
+        self._seen = [False] * len(self.params)
+        self._nseen = 0
+        self._dst = [None] * len(self.params)
+        for buf, _, fut in pending:
+            fut.set_result(buf)
+
     def _complete(self) -> None:
         if self.fused:
             if self._fused_applies():
                 return self._complete_fused()
+            self._dst = [None] * len(self.params)
+        if self._direct:
+            if self.direct_store_applies():
+                return self._complete_direct()
             self._dst = [None] * len(self.params)
         outs = self.powersgd.aggregate(self.views)  # leaves the new residual in self.views
         pending, self._pending = self._pending, []

@@ -44,10 +44,10 @@
  *    fp32/bf16 plans and at most 32 for fp64 plans (PSGD_ERR_VALUE at psgd_plan_create). A plan
  *    whose largest effective rank exceeds 32 is a WIDE plan (psgd_plan_is_wide): same P/Q layout,
  *    its own matrix-core kernels, none of the fused forms. psgd_compress, psgd_decompress,
- *    psgd_aggregate, psgd_aggregate_flat, psgd_aggregate_comm, the timing calls and every
- *    psgd_plan_* query take wide plans; psgd_plan_set_buckets with more than one bucket, the
- *    *_bucket calls, the building blocks and psgd_ipc_create refuse them (PSGD_ERR_VALUE,
- *    nothing is launched).
+ *    psgd_aggregate, psgd_aggregate_flat, psgd_aggregate_comm, psgd_aggregate_ipc (over a session
+ *    of psgd_ipc_create2), the timing calls and every psgd_plan_* query take wide plans;
+ *    psgd_plan_set_buckets with more than one bucket, the *_bucket calls, the building blocks and
+ *    psgd_ipc_create refuse them (PSGD_ERR_VALUE, nothing is launched).
  *  - Errors: every call returns a psgd_status; psgd_last_error() returns a thread-local message.
  *    PSGD_ERR_INDEX mirrors the reference's IndexError (no tensors, :118), PSGD_ERR_DTYPE its
  *    RuntimeError on unsupported dtypes (:189), PSGD_ERR_LAYOUT its RuntimeError on
@@ -223,6 +223,42 @@ typedef struct psgd_ipc_info {
     uint32_t peer_nonce_seen; /* the nonce in peer w's region header, read through the mapping */
 } psgd_ipc_info;
 int psgd_ipc_debug(psgd_plan* plan, int32_t peer, psgd_ipc_info* info);
+
+/* The exchange for WIDE plans (effective ranks 33-128), and its two-shot form.
+ * psgd_ipc_create keeps refusing a wide plan; psgd_ipc_create2 opens a session for either kind.
+ * `mode`: 0 one-shot, 1 two-shot, 2 auto. Checked in this order: a null pointer or a mode outside
+ * {0, 1, 2} PSGD_ERR_VALUE; an unbound plan PSGD_ERR_STATE; an fp64 plan PSGD_ERR_DTYPE; a plan
+ * of rank <= 32 with mode 1 PSGD_ERR_VALUE (their non-last exchanges take per-item forms; two-shot
+ * is not built for them); a negative flat_numel or a slot of 2^32 bytes or more PSGD_ERR_VALUE (the
+ * kernels' buffer descriptors are 32-bit). On a plan of rank <= 32 with mode 0 or 2 it IS
+ * psgd_ipc_create: the same region layout, flags, epochs, launches and results. On a wide plan it
+ * opens a session that psgd_ipc_open, psgd_ipc_close, psgd_ipc_status, psgd_ipc_debug and
+ * psgd_aggregate_ipc serve as above (psgd_aggregate_mixed_ipc[_dst] and psgd_aggregate_ipc_dst
+ * keep refusing wide plans). Every rank of a session passes the same mode.
+ *   One-shot: every rank reads all W slots whole, W * n floats per exchange of n floats, of which
+ *   (W - 1) * n are remote.
+ *   Two-shot: a reduce-scatter launch (rank r sums shard r of the W slots in rank order and
+ *   stores the sum, in place, into its own slot) and an all-gather launch (every rank copies the
+ *   other ranks' shards; on the last iteration it also sums the flat tail one-shot):
+ *   2 * (W - 1) / W * n remote floats per rank, a factor W / 2 fewer (byte arithmetic). Every
+ *   element is still summed in rank order, once, so the results are bitwise the one-shot ones
+ *   on every rank. A timed-out wait leaves NaN in the shard (slot and state) and in every output.
+ *   Auto: an exchange runs two-shot when the session's world is >= 3 and the factor is >= 512 KiB
+ *   (an unmeasured estimate). A 1-rank session is always one-shot.
+ * A wide plan's session uses two epochs per step on each iteration's flag word (2 * (step + 1) - 1
+ * for the reduce-scatter phase, 2 * (step + 1) for the all-gather phase and for every one-shot
+ * exchange), so psgd_aggregate_ipc then takes step < 2^31 - 1.
+ *   psgd_ipc_two_shot  1 where the open session runs the factor exchange of `side` (0: P, the odd
+ *                      iterations; 1: Q, the even ones) two-shot. PSGD_ERR_STATE without an open
+ *                      session.
+ *   psgd_ipc_shard     host only: the partition of n floats over `world_size` ranks the two-shot
+ *                      kernels use. Contiguous shards in units of 4 floats,
+ *                      ceil(ceil(n / 4) / world_size) quads each; the last non-empty shard is
+ *                      clipped to n, later shards are empty (count 0). PSGD_ERR_VALUE for a null
+ *                      pointer, n < 0, a world size outside 1..64 or a rank outside the world. */
+int psgd_ipc_create2(psgd_plan* plan, int64_t flat_numel, int32_t mode, void* handle_out);
+int psgd_ipc_two_shot(const psgd_plan* plan, int32_t side, int32_t* two_shot);
+int psgd_ipc_shard(int64_t n, int32_t world_size, int32_t rank, int64_t* begin, int64_t* count);
 
 /* Whole BasicPowerSGD.aggregate step for world size 1. */
 int psgd_aggregate(psgd_plan* plan, void* const* grads, void* out, int64_t step, void* stream);

@@ -62,6 +62,9 @@ _SIGNATURES = {
     "psgd_aggregate_comm": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_ipc_handle_bytes": ([_P_i64], _i32),
     "psgd_ipc_create": ([_vp, _i64, _vp], _i32),
+    "psgd_ipc_create2": ([_vp, _i64, _i32, _vp], _i32),
+    "psgd_ipc_two_shot": ([_vp, _i32, _P_i32], _i32),
+    "psgd_ipc_shard": ([_i64, _i32, _i32, _P_i64, _P_i64], _i32),
     "psgd_ipc_open": ([_vp, _i32, _i32, _vp], _i32),
     "psgd_aggregate_ipc": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
     "psgd_ipc_status": ([_vp, _P_i32], _i32),
@@ -330,6 +333,21 @@ class Plan:
         check(lib().psgd_ipc_create(self._h, flat_numel, buf))
         return bytes(buf)
 
+    def ipc_create2(self, flat_numel: int = 0, mode: int = 2) -> bytes:
+        """psgd_ipc_create2: a session for a plan of any rank up to 128. ``mode``: 0 one-shot, 1
+        two-shot (wide plans only), 2 auto. A plan of rank <= 32 gets ``ipc_create``'s session."""
+        n = _i64()
+        check(lib().psgd_ipc_handle_bytes(ctypes.byref(n)))
+        buf = (ctypes.c_uint8 * n.value)()
+        check(lib().psgd_ipc_create2(self._h, flat_numel, mode, buf))
+        return bytes(buf)
+
+    def ipc_two_shot(self, side: int) -> bool:
+        """psgd_ipc_two_shot: the open session runs the P-side (0) / Q-side (1) exchange two-shot."""
+        v = _i32()
+        check(lib().psgd_ipc_two_shot(self._h, side, ctypes.byref(v)))
+        return bool(v.value)
+
     def ipc_open(self, world: int, rank: int, handles: Sequence[bytes]) -> None:
         blob = b"".join(handles)
         arr = (ctypes.c_uint8 * len(blob)).from_buffer_copy(blob)
@@ -501,6 +519,14 @@ class Runs:
 
     def gather_list(self, sources, tensors, stream: int) -> None:
         check(lib().psgd_runs_gather_list(self._h, sources, tensors, stream))
+
+
+def ipc_shard(n: int, world: int, rank: int):
+    """psgd_ipc_shard: (begin, count) of rank ``rank``'s shard of an ``n``-float factor in the
+    two-shot exchange (host arithmetic only)."""
+    b, c = _i64(), _i64()
+    check(lib().psgd_ipc_shard(n, world, rank, ctypes.byref(b), ctypes.byref(c)))
+    return b.value, c.value
 
 
 def comm_unique_id() -> bytes:

@@ -377,6 +377,7 @@ struct WideArgs {
     float* yh;                // its history copy
     const RedItem* items;     // reduction items (mat, start, cnt, np)
     int32_t even;
+    float* xout;              // IPC exchange: the local out-factor also to this rank's slot, or null
 };
 hipError_t launch_wide_product(int dtype, int R, bool even, const WideArgs& a, int ntiles, hipStream_t s);
 hipError_t launch_wide_reduce(const WideArgs& a, int nitems, hipStream_t s);
@@ -588,6 +589,24 @@ struct XchgArgs {
     int32_t gram_r;
 };
 hipError_t launch_xchg(const XchgArgs& a, hipStream_t s);  // psgd_xchg.hip
+
+// Two-shot all-reduce of one factor over the same slots, flags and arguments (psgd_xchg2.hip;
+// sessions of psgd_ipc_create2 on a wide plan): k_xchg_rs sums this rank's shard of the W slots
+// into `dst` and, in place, into its own slot (epoch 2 * (step + 1) - 1); k_xchg_ag, the next
+// launch, copies every other rank's shard from that rank's slot and, on the last iteration, sums
+// the flat tail one-shot (epoch 2 * (step + 1)). launch_xchg_rs ignores the flat fields.
+// The partition (psgd_ipc_shard): contiguous shards of xchg_shard_quads(n, W) 16-byte quads, the
+// last non-empty one clipped to n, later ones empty.
+__host__ __device__ inline int64_t xchg_shard_quads(int64_t n, int32_t world) {
+    return ((n + 3) / 4 + world - 1) / world;
+}
+hipError_t launch_xchg_rs(const XchgArgs& a, hipStream_t s);
+hipError_t launch_xchg_ag(const XchgArgs& a, hipStream_t s);
+// psgd_ipc_create2, mode auto: an exchange runs two-shot when the session's world is >= 3 (at
+// W = 2 the remote bytes are equal and only the extra launch remains) and the factor is at least
+// this many bytes. DESIGN section 11's estimate ("factors above ~0.5 MB"): nobody has measured it,
+// and it cannot be measured on one GPU.
+constexpr int64_t kXchgTwoShotBytes = int64_t(512) << 10;
 
 // The LAST exchange of psgd_aggregate_mixed_ipc[_dst] when the step has a flat tail (k_xchg_mix,
 // psgd_xchg_mix.hip): the factor exactly as k_xchg (never the item / Gram form: those belong to

@@ -1,5 +1,6 @@
-// One-shot all-reduce over HIP IPC (psgd_ipc_*, psgd_aggregate_ipc; include/psgd.h): the
-// process-lifetime exchange arena, the exchange sessions of a plan and the step driver.
+// All-reduce over HIP IPC (psgd_ipc_*, psgd_aggregate_ipc; include/psgd.h): the process-lifetime
+// exchange arena, the exchange sessions of a plan (psgd_ipc_create; psgd_ipc_create2, which also
+// serves wide plans and their two-shot exchange) and the step driver.
 #include <unistd.h>
 
 #include <atomic>
@@ -154,6 +155,8 @@ int psgd::ipc_check(const psgd_plan* p, int64_t step) {
         return fail(PSGD_ERR_STATE, "an earlier IPC exchange wait timed out (a peer did not arrive within "
                                     "PSGD_IPC_SPIN); the exchange is invalid until psgd_ipc_close");
     if (step < 0 || step >= 0xffffffffLL) return fail(PSGD_ERR_VALUE, "step out of range (epochs are 32-bit)");
+    if (p->ipc_x2 && step >= 0x7fffffffLL)  // two epochs per step
+        return fail(PSGD_ERR_VALUE, "step out of range (a psgd_ipc_create2 session of a wide plan takes step < 2^31 - 1)");
     return PSGD_OK;
 }
 
@@ -179,7 +182,7 @@ int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t
     // starts even, else its own launch
     FlatArgs fa{};
     const bool ingest = mix && !dst;
-    const bool fold = has_flat && !ingest && p->even(step, 0);
+    const bool fold = has_flat && !ingest && p->even(step, 0) && !p->wide();  // wide products carry no flat pack
     float* flat_slot = p->xslot(step, last) + p->ipc_flat_off;
     if (has_flat) {
         if (int st = flat_args(f, unc, flat_slot, world, s, &fa)) return st;
@@ -230,7 +233,8 @@ int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t
             xa.flat_off = p->ipc_flat_off;
             xa.nflat = f->total;
         }
-        xa.epoch = uint64_t(step) + 1;
+        // sessions of psgd_ipc_create2 on a wide plan: two epochs per step (psgd_plan::ipc_x2)
+        xa.epoch = p->ipc_x2 ? 2 * (uint64_t(step) + 1) : uint64_t(step) + 1;
         xa.nonces = p->dev(p->ipc_nonces);
         xa.own_nonce = p->ipc_nonce;
         xa.spin_limit = spin;
@@ -246,6 +250,13 @@ int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t
             xm.flat_out = dst ? nullptr : flat_out;
             xm.unc_dst = dst ? dst->unc_dst : nullptr;
             PSGD_HIP(launch_xchg_mix(xa, xm, dst != nullptr, s));
+        } else if (p->ipc_two_shot(e ? 1 : 0)) {
+            // reduce-scatter on the first epoch of the step, all-gather (and the flat tail) on the
+            // second, as two launches: the kernel boundary drains the in-place shard stores
+            XchgArgs rs = xa;
+            rs.epoch = xa.epoch - 1;
+            PSGD_HIP(launch_xchg_rs(rs, s));
+            PSGD_HIP(launch_xchg_ag(xa, s));
         } else {
             PSGD_HIP(launch_xchg(xa, s));
         }
@@ -270,15 +281,16 @@ int psgd_ipc_handle_bytes(int64_t* bytes) {
     return PSGD_OK;
 }
 
-int psgd_ipc_create(psgd_plan* p, int64_t flat_numel, void* handle_out) {
-    if (!p || !handle_out) return fail(PSGD_ERR_VALUE, "null argument");
-    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
-    if (p->f64()) return fail(PSGD_ERR_DTYPE, "the IPC all-reduce takes fp32/bf16 plans");
-    if (p->wide()) return fail(PSGD_ERR_VALUE, "psgd_ipc_create: ranks above 32 are not supported there");
-    if (flat_numel < 0) return fail(PSGD_ERR_VALUE, "negative flat size");
+}  // extern "C"
+
+namespace {
+
+int64_t a64(int64_t x) { return (x + 63) & ~int64_t(63); }
+
+// the session behind psgd_ipc_create and psgd_ipc_create2, after their argument checks
+int ipc_create_checked(psgd_plan* p, int64_t flat_numel, void* handle_out) {
     if (!p->ipc_peer.empty()) return fail(PSGD_ERR_STATE, "exchange session open (psgd_ipc_close first)");
     DevScope scope(p->device);
-    auto a64 = [](int64_t x) { return (x + 63) & ~int64_t(63); };
     const int64_t flat_off = a64(std::max<int64_t>(p->fmax, 1));
     const int64_t slot = flat_off + a64(flat_numel);
     const size_t bytes = size_t(kXchgHeader) + size_t(2 * p->iters * slot) * sizeof(float);
@@ -322,6 +334,60 @@ int psgd_ipc_create(psgd_plan* p, int64_t flat_numel, void* handle_out) {
     std::memcpy(h, &c.handle, sizeof(hipIpcMemHandle_t));
     std::memcpy(h + sizeof(hipIpcMemHandle_t), &off64, sizeof(uint64_t));
     std::memcpy(h + sizeof(hipIpcMemHandle_t) + sizeof(uint64_t), &p->ipc_nonce, sizeof(uint32_t));
+    return PSGD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int psgd_ipc_create(psgd_plan* p, int64_t flat_numel, void* handle_out) {
+    if (!p || !handle_out) return fail(PSGD_ERR_VALUE, "null argument");
+    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
+    if (p->f64()) return fail(PSGD_ERR_DTYPE, "the IPC all-reduce takes fp32/bf16 plans");
+    if (p->wide()) return fail(PSGD_ERR_VALUE, "psgd_ipc_create: ranks above 32 are not supported there");
+    if (flat_numel < 0) return fail(PSGD_ERR_VALUE, "negative flat size");
+    if (int st = ipc_create_checked(p, flat_numel, handle_out)) return st;
+    p->ipc_x2 = false;
+    p->ipc_mode = 0;
+    return PSGD_OK;
+}
+
+int psgd_ipc_create2(psgd_plan* p, int64_t flat_numel, int32_t mode, void* handle_out) {
+    if (!p || !handle_out) return fail(PSGD_ERR_VALUE, "null argument");
+    if (mode < 0 || mode > 2) return fail(PSGD_ERR_VALUE, "psgd_ipc_create2: mode is 0 (one-shot), 1 (two-shot) or 2 (auto)");
+    if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
+    if (p->f64()) return fail(PSGD_ERR_DTYPE, "the IPC all-reduce takes fp32/bf16 plans");
+    if (!p->wide() && mode == 1)
+        return fail(PSGD_ERR_VALUE, "psgd_ipc_create2: the two-shot exchange serves ranks above 32 only");
+    if (flat_numel < 0) return fail(PSGD_ERR_VALUE, "negative flat size");
+    // the exchange kernels address a slot through 32-bit buffer descriptors and byte offsets
+    // (flat_numel first: the sum cannot overflow)
+    if (flat_numel >= (int64_t(1) << 30) ||
+        (a64(std::max<int64_t>(p->fmax, 1)) + a64(flat_numel)) * int64_t(sizeof(float)) >= (int64_t(1) << 32))
+        return fail(PSGD_ERR_VALUE, "psgd_ipc_create2: an exchange slot of 2^32 bytes or more");
+    if (int st = ipc_create_checked(p, flat_numel, handle_out)) return st;
+    p->ipc_x2 = p->wide();  // a narrow plan's session is psgd_ipc_create's in every respect
+    p->ipc_mode = p->wide() ? mode : 0;
+    return PSGD_OK;
+}
+
+int psgd_ipc_two_shot(const psgd_plan* p, int32_t side, int32_t* out) {
+    if (!p || !out) return fail(PSGD_ERR_VALUE, "null argument");
+    if (side != 0 && side != 1) return fail(PSGD_ERR_VALUE, "side is 0 (P) or 1 (Q)");
+    if (p->ipc_peer.empty()) return fail(PSGD_ERR_STATE, "psgd_ipc_open first");
+    *out = p->ipc_two_shot(side) ? 1 : 0;
+    return PSGD_OK;
+}
+
+int psgd_ipc_shard(int64_t n, int32_t world, int32_t rank, int64_t* begin, int64_t* count) {
+    if (!begin || !count) return fail(PSGD_ERR_VALUE, "null argument");
+    if (n < 0 || world < 1 || world > kMaxRanks || rank < 0 || rank >= world)
+        return fail(PSGD_ERR_VALUE, "bad size/world/rank");
+    const int64_t qf = (n + 3) / 4, per = xchg_shard_quads(n, world);
+    const int64_t q0 = std::min(per * rank, qf), q1 = std::min(q0 + per, qf);
+    *begin = 4 * q0;
+    *count = std::max<int64_t>(std::min(4 * q1, n) - 4 * q0, 0);
     return PSGD_OK;
 }
 

@@ -343,6 +343,19 @@ struct psgd_plan {
     int ipc_world = 0, ipc_rank = -1;
     int64_t ipc_slot = 0, ipc_flat_off = 0, ipc_flat_cap = 0;
     uint32_t ipc_nonce = 0;  // this rank's exchange session (psgd_ipc_create)
+    // sessions of psgd_ipc_create2 on a wide plan (ipc_x2): every exchange of a step takes two epochs,
+    // 2 * (step + 1) - 1 (the reduce-scatter phase of a two-shot exchange) and 2 * (step + 1) (its
+    // all-gather phase, and every one-shot exchange); ipc_mode: 0 one-shot, 1 two-shot, 2 auto.
+    // Sessions of psgd_ipc_create: false, epoch step + 1.
+    bool ipc_x2 = false;
+    int32_t ipc_mode = 0;
+    // the factor exchange of side 0 (P, odd iterations) / 1 (Q, even ones) of the open session runs
+    // two-shot (psgd_ipc_two_shot; the driver decides from this)
+    bool ipc_two_shot(int side) const {
+        if (!ipc_x2 || ipc_world < 2 || ipc_mode == 0) return false;
+        if (ipc_mode == 1) return true;
+        return ipc_world >= 3 && (side ? qtot : ptot) * int64_t(sizeof(float)) >= kXchgTwoShotBytes;
+    }
     // sticky timeout word of the exchange waits: pinned host memory mapped into the device
     // (k_xchg stores 1 with a system-scope store), so every psgd_aggregate_ipc call can check it
     // without synchronising; cleared only by psgd_ipc_close

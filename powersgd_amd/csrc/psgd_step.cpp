@@ -183,7 +183,9 @@ int decompress_f64(psgd_plan* p, void* const* grads, void* out, int64_t step, in
 // previous iteration goes to history slot 2, the orthonormal one to slot 0), the product with
 // G_k formed on the matrix core, then the fixed-order partial reduction (both parities: the odd
 // product is split over column strips as well). psgd_compress never writes the gradients.
-int compress_wide(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s) {
+// `xout` (psgd_aggregate_ipc): the reduction also writes the local out-factor into this rank's
+// exchange slot.
+int compress_wide(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s, float* xout) {
     if (int st = refresh_pointers(p, grads, s)) return st;
     const bool even = p->even(step, it);
     WideOrthArgs oa{};
@@ -211,6 +213,7 @@ int compress_wide(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hi
     a.yh = p->hist(1, it);
     a.items = p->dev(even ? p->red_even : p->red_odd);
     a.even = even ? 1 : 0;
+    a.xout = xout;
     PSGD_HIP(launch_wide_product(p->dtype, p->rbucket, even, a, int(even ? p->wide_even.size() : p->wide_odd.size()), s));
     PSGD_HIP(launch_wide_reduce(a, int(even ? p->red_even.size() : p->red_odd.size()), s));
     return PSGD_OK;
@@ -537,7 +540,7 @@ hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArg
 
 int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s, StepCtx c) {
     if (p->f64()) return compress_f64(p, grads, step, it, s);
-    if (p->wide()) return compress_wide(p, grads, step, it, s);
+    if (p->wide()) return compress_wide(p, grads, step, it, s, c.xout);
     if (int st = refresh_pointers(p, grads, s)) return st;
     const Iter i{p, step, it, p->route(step, it, c), c.span ? *c.span : p->full_span(), s, c};
     if (int st = orth_stage(i)) return st;

@@ -221,6 +221,7 @@ __global__ __launch_bounds__(kBlock) void k_wide_reduce(WideArgs a) {
     const int64_t off = (a.even ? d.qoff : d.poff) + e;
     a.y[off] = s;
     a.yh[off] = s;
+    if (a.xout) st_slot(a.xout + off, s);  // the IPC exchange's hand-off (write-through), as k_reduce
 }
 
 // --------------------------------------------------------------------------- apply --

@@ -1,6 +1,6 @@
 // The flag and wait protocol of the one-shot all-reduce over IPC-mapped exchange buffers, shared by
-// its kernels (k_xchg, psgd_xchg.hip; k_xchg_mix, psgd_xchg_mix.hip), and the rank-order sum of a
-// 16-byte quad of the W slots.
+// its kernels (k_xchg, psgd_xchg.hip; k_xchg_mix, psgd_xchg_mix.hip) and by the two-shot form's
+// (k_xchg_rs, k_xchg_ag, psgd_xchg2.hip), and the rank-order sum of a 16-byte quad of the W slots.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -18,8 +18,9 @@ Differences, all deliberate:
   the reference, torch's default dtype must then be float64 (P/Q follow it, :241-251).
 * The effective rank ``min(rank, n, m)`` of a matrix is at most 128 for float32 / bfloat16
   gradients and at most 32 for float64 ones (the reference has no limit); the constructor raises
-  ``ValueError`` beyond. Above 32, a step keeps one collective per iteration (no buckets) and the
-  IPC exchange (``PSGD_COMM=ipc``) is not available.
+  ``ValueError`` beyond. Above 32, a step keeps one collective per iteration (no buckets); over
+  the IPC exchange (``PSGD_COMM=ipc``) its large factor exchanges run two-shot (reduce-scatter +
+  all-gather; ``PSGD_IPC_TWO_SHOT=0`` / ``1`` forces one form, unset chooses per factor).
 * Returned compressed outputs are views of one flat buffer (allocated fresh per call)
   instead of separate ``empty_like`` tensors; uncompressed outputs are views in the
   reference too.
@@ -334,12 +335,18 @@ class BasicPowerSGD(Aggregator):
         uncompressed values), all-gather the IPC handles and open the peers' buffers."""
         if self._ipc_open:
             return
-        if self._plan.is_wide():
-            raise RuntimeError("PSGD_COMM=ipc supports effective ranks up to 32; this plan's rank exceeds that "
-                               "(ranks 33-128 run over PSGD_COMM=rccl or PSGD_COMM=torch)")
         dist = torch.distributed
         world = dist.get_world_size()
-        handle = self._plan.ipc_create(flat_numel)
+        if self._plan.is_wide():
+            # effective ranks 33-128: a session of psgd_ipc_create2, whose large factor exchanges
+            # may run two-shot (reduce-scatter + all-gather). PSGD_IPC_TWO_SHOT=0 / 1 forces the
+            # form, unset is auto; read once, here, and the same on every rank
+            forced = os.environ.get("PSGD_IPC_TWO_SHOT")
+            if forced not in (None, "", "0", "1"):
+                raise ValueError(f"PSGD_IPC_TWO_SHOT={forced!r}: 0, 1 or unset")
+            handle = self._plan.ipc_create2(flat_numel, int(forced) if forced else 2)
+        else:
+            handle = self._plan.ipc_create(flat_numel)
         handles: List = [None] * world
         dist.all_gather_object(handles, handle)
         err = None

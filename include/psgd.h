@@ -402,18 +402,21 @@ int psgd_runs_gather_list(psgd_runs* runs, void* const* sources, void* const* te
  *   4. out_bf16[j] = bf16(avg[j])                   round to nearest even
  * but the two element-wise stages run inside the codec's own gradient passes where they can:
  *   output fold  the step's final pass (k_final_proj / k_final_odd / k_apply) stores its output as
- *                bf16; the residual stays fp32. Every step of an eligible plan.
+ *                bf16; the residual stays fp32. Every step of an eligible plan. At rank buckets 16
+ *                and 32 that pass is k_apply's matrix-core tile (and its VALU fallback wherever
+ *                k_apply<float> takes it: the choice follows the residual's alignment and the
+ *                plan's output offset, never the bf16 buffer).
  *   ingest fold  the single-pass k_final_odd (num_iters_per_step = 1 on an odd step, ranks 1 and
  *                2: the step's only gradient pass) loads residual + float(g) and stores +0.0 to g
  *                beside its own residual. On every other step the library launches the run-table
  *                ADD itself, first (the same fold in k_even was measured slower than that ADD and
  *                is not kept; the odd-even pass and the unfused odd product have none).
- * `plan`: a bound PSGD_F32 plan driven at world size 1, rank bucket 1, 2 or 4 (largest effective
- * rank <= 4), one bucket; `residual[i]`: its fp32 tensors (the plan's gradients: alignment as for
+ * `plan`: a bound PSGD_F32 plan driven at world size 1, rank bucket 1, 2, 4, 16 or 32 (largest
+ * effective rank 1-4 or 9-32), one bucket; `residual[i]`: its fp32 tensors (the plan's gradients: alignment as for
  * psgd_aggregate); `grads_bf16[i]`: the fresh bf16 gradients, the plan's shapes, 2-byte aligned
  * (8-byte aligned tensors of m % 4 == 0 matrices take vector accesses); `out_bf16`: a dense bf16
  * buffer, 16-byte aligned, tensor i at element offset psgd_plan_output_offset(i). Any other plan
- * (rank bucket above 4, wide, fp64 or bf16 dtype, more than one bucket): PSGD_ERR_VALUE before
+ * (rank bucket 8, wide: ranks above 32, fp64 or bf16 dtype, more than one bucket): PSGD_ERR_VALUE before
  * anything is launched, and psgd_plan_mixed_folds reports 0 / 0.
  * Every mixed kernel instance is admitted like the fused final pass (at least two waves per SIMD,
  * no scratch; asked of the runtime). Without an admitted ingest instance that fold is dropped (the
@@ -461,8 +464,8 @@ int psgd_plan_mixed_folds(const psgd_plan* plan, int64_t step, int32_t* fold_in,
  *                first collective; flat_out_bf16 = bf16(stage) in the leading workgroups of the
  *                final launch (a launch of its own after the world-size-1 instance).
  * Arguments as psgd_aggregate_mixed_flat (flat null or empty: no uncompressed tensors) and
- * psgd_aggregate_comm. Eligible: a bound PSGD_F32 plan, rank bucket 1, 2 or 4, not wide, one
- * bucket, whose final-pass instance of BOTH step parities is admitted (at least two waves per SIMD,
+ * psgd_aggregate_comm. Eligible: a bound PSGD_F32 plan, rank bucket 1, 2, 4, 16 or 32 (not 8), not
+ * wide, one bucket, whose final-pass instance of BOTH step parities is admitted (at least two waves per SIMD,
  * no scratch; asked of the runtime) for the communicator's world size. Anything else:
  * PSGD_ERR_VALUE before anything is launched or any collective issued, the communicator stays
  * usable, and psgd_plan_mixed_folds_comm reports 0 / 0. A poisoned communicator is refused at
@@ -537,8 +540,8 @@ int psgd_plan_mixed_folds_dst(const psgd_plan* plan, int64_t step, int32_t world
  *   output fold  every step: the output pass after the exchanges stores bf16 (the instances of
  *                psgd_aggregate_mixed_comm / _comm_dst: k_apply with two term sets, k_lowrank_out
  *                after a fused k_final_odd, the world-size-1 k_apply in a 1-rank session).
- * Eligible: as psgd_aggregate_mixed_comm / _comm_dst (a bound PSGD_F32 plan, rank bucket 1, 2 or
- * 4, not wide, one bucket, the final-pass instance of BOTH step parities admitted for the
+ * Eligible: as psgd_aggregate_mixed_comm / _comm_dst (a bound PSGD_F32 plan, rank bucket 1, 2, 4,
+ * 16 or 32, not wide, one bucket, the final-pass instance of BOTH step parities admitted for the
  * session's world size: psgd_plan_mixed_folds_comm / psgd_plan_mixed_folds_dst answer for it), with
  * an open exchange session (psgd_ipc_open), flat->total within the session's flat_numel,
  * step < 2^32 - 1 and no timed-out wait pending. An ineligible plan, an oversized flat plan, an

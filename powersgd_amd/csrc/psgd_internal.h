@@ -452,9 +452,9 @@ struct RunsMixArgs {
 };
 hipError_t launch_runs_mix(int bucket_dtype, int tensor_dtype, int mode, const RunsMixArgs& a, hipStream_t s);
 
-// psgd_aggregate_mixed (fp32 plans at world size 1, rank buckets 1 / 2 / 4): the fp32 codec on an
-// fp32 error-feedback residual fed by bf16 gradients, with the two element-wise passes around it
-// folded into its own gradient passes. The mixed kernel instances take this second argument
+// psgd_aggregate_mixed (fp32 plans at world size 1, rank buckets 1 / 2 / 4 / 16 / 32): the fp32
+// codec on an fp32 error-feedback residual fed by bf16 gradients, with the two element-wise passes
+// around it folded into its own gradient passes. The mixed kernel instances take this second argument
 // beside the codec's own (whose structs, and so every other instance, stay as they are):
 //   output fold   the step's final pass (k_final_odd / k_final_proj / k_apply) stores its output
 //                 as bf16 (StIo<bf16_t>; `out` and the flat buffer are bf16 buffers); the residual
@@ -516,6 +516,16 @@ hipError_t launch_lowrank_mix_dst(int R, int nterms, const ApplyArgs& a, const M
                                   int ntiles, hipStream_t s, int* waves);
 hipError_t launch_apply_mix_dst(int R, int nterms, const ApplyArgs& a, int ntiles, hipStream_t s, int* waves);
 hipError_t launch_flat_round_dst(const FlatArgs& a, const MixArgs& x, void* const* unc_dst, hipStream_t s);
+// psgd_mixed_mfma.hip: rank buckets 16 / 32 of launch_apply_mix, launch_apply_mix_w,
+// launch_apply_mix_w_dst and launch_apply_mix_dst (which hand them their cases 16 and 32): the
+// matrix-core tile of k_apply<float> with the output stored as bf16, its VALU fallback where
+// k_apply takes it. One instance per (R, term sets, ONT / destination form): no terms are cached
+// at these ranks. Any other R: hipErrorInvalidValue (rank bucket 8 has no mixed instance).
+hipError_t launch_apply_mix_mc(int R, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s, int* waves);
+hipError_t launch_apply_mix_w_mc(int R, const ApplyArgs& a, const MixArgs& x, int ntiles, hipStream_t s, int* waves);
+hipError_t launch_apply_mix_w_dst_mc(int R, const ApplyArgs& a, const MixArgs& x, void* const* unc_dst, int ntiles,
+                                     hipStream_t s, int* waves);
+hipError_t launch_apply_mix_dst_mc(int R, const ApplyArgs& a, int ntiles, hipStream_t s, int* waves);
 
 // psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst (the default fp32 DDP hook's one-call form): the
 // final pass of an fp32 plan (rank buckets 1-32) stores each tensor's fp32 average at the tensor's

@@ -32,10 +32,14 @@
 
 namespace {
 
-// rank buckets 1 / 2 / 4, fp32, not wide, one bucket
+// rank buckets 1 / 2 / 4 (VALU tiles) and 16 / 32 (matrix-core tiles, psgd_mixed_mfma.hip), fp32,
+// not wide, one bucket. Rank bucket 8 (the VALU tile whose register-cached two-set instances sit at
+// the scratch edge) and wide plans (ranks 33-128) have no mixed instance
 const char* ineligible(const psgd_plan* p) {
     if (p->dtype != PSGD_F32) return "psgd_aggregate_mixed takes an fp32 plan (the fp32 residual of bf16 gradients)";
-    if (p->wide() || p->rbucket > 4) return "psgd_aggregate_mixed serves rank buckets 1, 2 and 4";
+    const int rb = p->rbucket;
+    if (p->wide() || !(rb == 1 || rb == 2 || rb == 4 || rb == 16 || rb == 32))
+        return "psgd_aggregate_mixed serves rank buckets 1, 2, 4, 16 and 32 (not 8, not ranks above 32)";
     if (p->spans.size() > 1) return "psgd_aggregate_mixed takes a plan of one bucket";
     return nullptr;
 }

@@ -9,6 +9,8 @@ hipError_t launch_apply_mix(int R, int nterms, const ApplyArgs& a, const MixArgs
         case 1: return dispatch_apply_mix_r<1>(nterms, a, x, ntiles, s, waves);
         case 2: return dispatch_apply_mix_r<2>(nterms, a, x, ntiles, s, waves);
         case 4: return dispatch_apply_mix_r<4>(nterms, a, x, ntiles, s, waves);
+        case 16:
+        case 32: return launch_apply_mix_mc(R, a, x, ntiles, s, waves);  // psgd_mixed_mfma.hip
         default: return hipErrorInvalidValue;
     }
 }

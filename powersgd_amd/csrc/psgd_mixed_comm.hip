@@ -53,6 +53,8 @@ hipError_t launch_apply_mix_w(int R, int nterms, const ApplyArgs& a, const MixAr
         case 1: return dispatch_apply_mix_w<1>(nterms, a, x, ntiles, s, waves);
         case 2: return dispatch_apply_mix_w<2>(nterms, a, x, ntiles, s, waves);
         case 4: return dispatch_apply_mix_w<4>(nterms, a, x, ntiles, s, waves);
+        case 16:
+        case 32: return launch_apply_mix_w_mc(R, a, x, ntiles, s, waves);  // psgd_mixed_mfma.hip
         default: return hipErrorInvalidValue;
     }
 }

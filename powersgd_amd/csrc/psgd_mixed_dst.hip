@@ -120,6 +120,8 @@ hipError_t launch_apply_mix_w_dst(int R, int nterms, const ApplyArgs& a, const M
         case 1: return dispatch_apply_mix_w_dst<1>(nterms, a, x, unc_dst, ntiles, s, waves);
         case 2: return dispatch_apply_mix_w_dst<2>(nterms, a, x, unc_dst, ntiles, s, waves);
         case 4: return dispatch_apply_mix_w_dst<4>(nterms, a, x, unc_dst, ntiles, s, waves);
+        case 16:
+        case 32: return launch_apply_mix_w_dst_mc(R, a, x, unc_dst, ntiles, s, waves);  // psgd_mixed_mfma.hip
         default: return hipErrorInvalidValue;
     }
 }
@@ -138,6 +140,8 @@ hipError_t launch_apply_mix_dst(int R, int nterms, const ApplyArgs& a, int ntile
         case 1: return dispatch_apply_mix_dst<1>(nterms, a, ntiles, s, waves);
         case 2: return dispatch_apply_mix_dst<2>(nterms, a, ntiles, s, waves);
         case 4: return dispatch_apply_mix_dst<4>(nterms, a, ntiles, s, waves);
+        case 16:
+        case 32: return launch_apply_mix_dst_mc(R, a, ntiles, s, waves);  // psgd_mixed_mfma.hip
         default: return hipErrorInvalidValue;
     }
 }

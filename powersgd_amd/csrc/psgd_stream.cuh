@@ -1363,12 +1363,19 @@ struct ApplyMfmaLds {
 
 // DST (psgd_apply_dst.hip, T = float): the output goes to a.odst[d.tensor], 4-byte aligned or
 // better; kDstElem stores a row's quad as four 4-byte stores (the kernel picks per tile).
-template <typename T, int R, bool SHARED, bool ONT, int DST = 0>
+// TO (the mixed instances, psgd_mixed_mfma.hip: T = float, TO = bf16_pin_t): the output's element
+// type. The output descriptor spans the tile's rows in sizeof(TO) bytes and a row quad is one
+// 8-byte store (dense, kDstVec) or four 2-byte stores (kDstElem, a destination that is not 8-byte
+// aligned: dst_al8); the values are pinned as the fp32 instance hands them to its store before
+// they are rounded (bf16_pin_t). The loads, the staging, the MFMA sequence and the residual store
+// are the fp32 instance's.
+template <typename T, int R, bool SHARED, bool ONT, int DST = 0, typename TO = T>
 __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDesc& d, const Tile& t, float* qs) {
     constexpr int KQ = R / 4;
     constexpr int RP = ApplyMfmaLds<R>::RP;
     constexpr int NS = SHARED ? 1 : 2;
     constexpr uint32_t s = sizeof(T);
+    constexpr bool kOwnOut = !std::is_same<TO, T>::value;  // the output has its own offsets
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ri = lane & 15, cq = lane >> 4;
     const int r = d.r;
@@ -1405,11 +1412,11 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
     __syncthreads();
     T* const Gp = static_cast<T*>(a.grads[t.tensor]);
     T* const Dp = static_cast<T*>(a.rdst ? a.rdst[d.tensor] : a.grads[t.tensor]);
-    T* const Op = a.odst ? static_cast<T*>(a.odst[d.tensor]) : static_cast<T*>(a.out) + d.out_off;
+    TO* const Op = a.odst ? static_cast<TO*>(a.odst[d.tensor]) : static_cast<TO*>(a.out) + d.out_off;
     const uint32_t tb = uint32_t((row_end - row_begin) * int64_t(m) * int64_t(s));
     const rsrc_t rG = make_rsrc(Gp + row_begin * m, tb);
     const rsrc_t rD = make_rsrc(Dp + row_begin * m, tb);
-    const rsrc_t rO = make_rsrc(Op + row_begin * m, tb);
+    const rsrc_t rO = make_rsrc(Op + row_begin * m, uint32_t((row_end - row_begin) * int64_t(m) * int64_t(sizeof(TO))));
     const uint32_t cofs = active ? uint32_t(col) * s : kOob;
     const uint32_t rstride = uint32_t(m) * s;
     const bool pvec = r == R && (d.poff & 3) == 0;
@@ -1470,8 +1477,23 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
             }
             const uint32_t off = (rb + v) * rstride + cofs;
             st_vec<T>(rD, off, xo);
-            if constexpr (DST != 0) st_vec_dstf<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, oo);
-            else st_vec<T, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, oo);
+            if constexpr (kOwnOut) {
+                // The output's offset in TO bytes. The residual's `off` leaves its descriptor by
+                // adding kOob (an inactive lane) or by its row term alone (a row past row_end);
+                // halved for a 2-byte output, the row term of a row past the end still exceeds the
+                // smaller descriptor, but kOob + row term is only safe from wrapping back into it
+                // while (rows + 15) * m * sizeof(TO) < 2^31, which the plan bounds for the tile
+                // (rows * m * 4 < 2^31) and not for the up to 15 rows past it. So the test is
+                // explicit: in range, an offset below the descriptor's size (< 2^30); else kOob.
+                const bool in = active && b0 + 4 * cq + v < row_end;
+                const uint32_t oo_off = in ? ((rb + v) * uint32_t(m) + uint32_t(col)) * uint32_t(sizeof(TO)) : kOob;
+                if constexpr (DST != 0) st_vec_dst<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, oo_off, oo);
+                else st_vec<TO, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, oo_off, oo);
+            } else if constexpr (DST != 0) {
+                st_vec_dstf<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, oo);
+            } else {
+                st_vec<T, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, oo);
+            }
         }
     }
     __syncthreads();  // qs is staged again by the next tile of this workgroup (none today)
@@ -1512,11 +1534,44 @@ __global__ __launch_bounds__(kBlock) void k_apply(ApplyArgs a) {
     apply_tile<T, R, NI, SHARED, 1, ONT>(a, d, t);
 }
 
+// A tile of the mixed final passes at rank buckets 16 / 32 (psgd_mixed_mfma.hip): k_apply<float, R,
+// -1, SHARED, ONT>'s R >= 16 body with the output stored as bf16, dense (ODST false) or at the
+// tensor's destination a.odst (ODST: the store form per tile, dst_al8, workgroup-uniform).
+// The matrix-core tile and its VALU fallback sum in different orders, so the choice between them
+// decides the bits: it is the one k_apply<float, R, ...> makes on the same step of the three-stage
+// flow, whose `rows` holds the residual's pointer (its gradient table is the residual's) and the
+// fp32 slab's term out + d.out_off. There is no fp32 slab here; its term is taken as k_apply_dst
+// takes it, the plan's offset alone: every entry that writes a slab refuses a base that is not
+// 16-byte aligned (check_out, psgd_plan.h: psgd_decompress, psgd_aggregate*, the communicator and
+// IPC forms), and the Python layer's OutputSlab (psgd_host.cpp) is a fresh allocation of the
+// caching allocator (512-byte aligned), so base + out_off is 16-byte aligned exactly when
+// out_off * 4 is. Neither the bf16 output pointer nor a destination view enters the choice.
+template <int R, bool SHARED, bool ONT, bool ODST>
+__device__ __forceinline__ void apply_mix_tile_mc(const ApplyArgs& a, const MatDesc& d, const Tile& t) {
+    static_assert(R == 16 || R == 32, "matrix-core apply tile: rank buckets 16 and 32");
+    __shared__ __attribute__((aligned(16))) float qs[ApplyMfmaLds<R>::floats];
+    constexpr int NS = SHARED ? 1 : 2;
+    const uintptr_t rows = reinterpret_cast<uintptr_t>(a.grads[t.tensor]) |
+                           reinterpret_cast<uintptr_t>(a.rdst ? a.rdst[d.tensor] : a.grads[t.tensor]) |
+                           uintptr_t(d.out_off) * sizeof(float);
+    if ((d.m & 3) == 0 && (rows & (4 * sizeof(float) - 1)) == 0 && a.nterms * NS <= kApplyMfmaSets) {
+        if constexpr (!ODST)
+            apply_tile_mfma<float, R, SHARED, ONT, 0, bf16_pin_t>(a, d, t, qs);
+        else if (dst_al8(a, d, t))
+            apply_tile_mfma<float, R, SHARED, ONT, kDstVec, bf16_pin_t>(a, d, t, qs);
+        else
+            apply_tile_mfma<float, R, SHARED, ONT, kDstElem, bf16_pin_t>(a, d, t, qs);
+        return;
+    }
+    apply_tile<float, R, -1, SHARED, 1, ONT, bf16_pin_t, ODST ? kDstVec : 0>(a, d, t);
+}
+
 // The final pass of psgd_aggregate_mixed (MixArgs): k_apply's world-size-1 form (SHARED) on an
-// fp32 residual with the output stored as bf16, the flat items as flat_mix_item. Ranks 1 / 2 / 4.
+// fp32 residual with the output stored as bf16, the flat items as flat_mix_item. Rank buckets
+// 1 / 2 / 4 (the VALU tiles) and 16 / 32 (apply_mix_tile_mc).
 template <int R, int NI, bool ONT>
 __global__ __launch_bounds__(kBlock) void k_apply_mix(ApplyArgs a, MixArgs x) {
-    static_assert(R <= 4, "mixed instances: rank buckets 1, 2 and 4");
+    static_assert(R <= 4 || R >= 16, "mixed instances: rank buckets 1, 2, 4, 16 and 32");
     const int nf = a.flat.nitems;
     if (int(blockIdx.x) < nf) {
         flat_mix_item<kBlock>(a.flat, x.unc_src, blockIdx.x);
@@ -1524,10 +1579,15 @@ __global__ __launch_bounds__(kBlock) void k_apply_mix(ApplyArgs a, MixArgs x) {
     }
     const Tile t = a.tiles[blockIdx.x - nf];
     const MatDesc d = a.mats[t.mat];
-    if (d.vec)
-        apply_tile<float, R, NI, true, 4, ONT, bf16_pin_t>(a, d, t);
-    else
-        apply_tile<float, R, NI, true, 1, ONT, bf16_pin_t>(a, d, t);
+    if constexpr (R >= 16) {
+        static_assert(NI == -1, "ranks 16 / 32 cache no terms (apply_ni)");
+        apply_mix_tile_mc<R, true, ONT, false>(a, d, t);
+    } else {
+        if (d.vec)
+            apply_tile<float, R, NI, true, 4, ONT, bf16_pin_t>(a, d, t);
+        else
+            apply_tile<float, R, NI, true, 1, ONT, bf16_pin_t>(a, d, t);
+    }
 }
 
 // The final pass of psgd_aggregate_mixed_comm at world size > 1: k_apply<float, R, NI, false> (two
@@ -1536,7 +1596,7 @@ __global__ __launch_bounds__(kBlock) void k_apply_mix(ApplyArgs a, MixArgs x) {
 // flat_round_item. out_nt is 0 at W > 1: no ONT instance.
 template <int R, int NI>
 __global__ __launch_bounds__(kBlock) void k_apply_mix_w(ApplyArgs a, MixArgs x) {
-    static_assert(R <= 4, "mixed instances: rank buckets 1, 2 and 4");
+    static_assert(R <= 4 || R >= 16, "mixed instances: rank buckets 1, 2, 4, 16 and 32");
     const int nf = a.flat.nitems;
     if (int(blockIdx.x) < nf) {
         flat_round_item<kBlock>(a.flat, x.stage, blockIdx.x);
@@ -1544,10 +1604,15 @@ __global__ __launch_bounds__(kBlock) void k_apply_mix_w(ApplyArgs a, MixArgs x) 
     }
     const Tile t = a.tiles[blockIdx.x - nf];
     const MatDesc d = a.mats[t.mat];
-    if (d.vec)
-        apply_tile<float, R, NI, false, 4, false, bf16_pin_t>(a, d, t);
-    else
-        apply_tile<float, R, NI, false, 1, false, bf16_pin_t>(a, d, t);
+    if constexpr (R >= 16) {
+        static_assert(NI == -1, "ranks 16 / 32 cache no terms (apply_ni)");
+        apply_mix_tile_mc<R, false, false, false>(a, d, t);
+    } else {
+        if (d.vec)
+            apply_tile<float, R, NI, false, 4, false, bf16_pin_t>(a, d, t);
+        else
+            apply_tile<float, R, NI, false, 1, false, bf16_pin_t>(a, d, t);
+    }
 }
 
 // resident waves per SIMD of a kernel at NT threads per workgroup; 0 when it uses scratch

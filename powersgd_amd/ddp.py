@@ -78,7 +78,7 @@ class PowerSGDState:
     DDP bucket, so no fp32 output slab is written and no per-bucket gather runs. Bit for bit the
     three stages it replaces. It applies on a compressing step, in a process group that runs over
     the library's own communicator or over the IPC exchange (not ``PSGD_COMM=torch``, not gloo
-    without the IPC exchange), on a plan the call serves (rank bucket 1 / 2 / 4); every other
+    without the IPC exchange), on a plan the call serves (rank bucket 1 / 2 / 4 / 16 / 32; not 8, not ranks above 32); every other
     completion runs the three stages (``fused_folds()`` tells which).
 
     ``state.direct_store = True`` (float32 parameters with a float32 residual, ``fused=False``; set

@@ -17,7 +17,8 @@ next backward accumulates fresh gradients only. Cost against ``PowerSGD`` on the
 gradients: the two element-wise passes, an fp32 codec step, 4 bytes of state per parameter.
 
 ``fused=True`` runs the same step as ONE library call (psgd_aggregate_mixed, include/psgd.h)
-wherever it applies (one process, a compressing step, rank bucket 1 / 2 / 4): the codec's final
+wherever it applies (one process, a compressing step, rank bucket 1 / 2 / 4 / 16 / 32; rank bucket
+8 and ranks above 32 run the three stages): the codec's final
 pass stores the bf16 averages itself (no GATHER pass), and where a step is one gradient pass
 (one iteration per step, odd steps) that pass also ingests the bf16 gradients (no ADD pass; on the
 other steps the library launches the ADD). In a process group that runs over the library's own RCCL

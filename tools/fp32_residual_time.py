@@ -15,7 +15,9 @@ unfused spread. ``by_step_parity`` splits every flow by the codec step's parity,
 took there: where the parities fold differently (resnet50_i1: both folds on odd steps, the output
 fold alone on even ones) the gain of each fold can be read against its separate pass.
 
-usage: python tools/fp32_residual_time.py [--rounds N] [--warmup N] [--out FILE] [workload ...]
+usage: python tools/fp32_residual_time.py [--rounds N] [--warmup N] [--rank R] [--out FILE] [workload ...]
+--rank R: the workloads at rank R instead of their own (16 / 32: the matrix-core final pass, which
+has no ingest fold, so there ``fused_out_only`` is the same flow as ``fused``: an A/A control).
 workloads: cfg4 (the cfg4_llama_r2_bf16 shapes), resnet50 (ResNet-50 shapes, rank 2, two
 iterations, bf16) and resnet50_i1 (the same with one iteration per step), all by default."""
 import argparse
@@ -45,8 +47,8 @@ def quartiles(xs):
             "min_ms": round(min(xs), 5), "max_ms": round(max(xs), 5)}
 
 
-def run(name, rounds, warmup):
-    w = WORKLOADS[name]
+def run(name, rounds, warmup, rank=None):
+    w = dict(WORKLOADS[name], **({} if rank is None else {"rank": rank}))
     dev = torch.device("cuda:0")
     bf16 = torch.bfloat16
     cfg = Config(w["rank"], w["mcr"], w["iters"], 0)
@@ -111,11 +113,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--rank", type=int, default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("workloads", nargs="*", default=list(WORKLOADS))
     a = ap.parse_args()
     out = {"tool": "tools/fp32_residual_time.py", "device": torch.cuda.get_device_name(0),
-           "results": [run(n, a.rounds, a.warmup) for n in a.workloads]}
+           "results": [run(n, a.rounds, a.warmup, a.rank) for n in a.workloads]}
     text = json.dumps(out, indent=1)
     print(text)
     if a.out:

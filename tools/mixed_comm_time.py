@@ -20,7 +20,7 @@ as faster only when its median beats the unfused median by more than the unfused
 --unfused-only  time the unfused flow alone (a build without the fused communicator call).
 
 usage: python tools/mixed_comm_time.py --comm stub|rccl [--world W] [--rounds N] [--warmup N]
-                                       [--unfused-only] [--out FILE] [workload ...]
+                                       [--rank R] [--unfused-only] [--out FILE] [workload ...]
 workloads: cfg4 (the cfg4_llama_r2_bf16 shapes, rank 2, one iteration) and resnet50 (ResNet-50
 shapes, rank 2, two iterations, bf16), both by default."""
 import argparse
@@ -43,6 +43,8 @@ def quartiles(xs):
 
 
 def run(name, w, a):
+    if a.rank is not None:
+        w = dict(w, rank=a.rank)
     from powersgd_amd import Config, Fp32ResidualPowerSGD, _lib
 
     dev = torch.device("cuda:0")
@@ -112,6 +114,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--unfused-only", action="store_true")
+    ap.add_argument("--rank", type=int, default=None, help="the workloads at this rank instead of their own")
     ap.add_argument("--out", default=None)
     ap.add_argument("workloads", nargs="*", default=["cfg4", "resnet50"])
     a = ap.parse_args()

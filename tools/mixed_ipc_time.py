@@ -15,7 +15,7 @@ its median beats the unfused median by more than the unfused spread.
 One GPU, W processes: the exchange's loads and flags stay on the device, the processes' kernels
 share its CUs. No cross-GPU traffic is measured.
 
-usage: python tools/mixed_ipc_time.py [--world W] [--rounds N] [--warmup N] [--out FILE] [workload ...]
+usage: python tools/mixed_ipc_time.py [--world W] [--rounds N] [--warmup N] [--rank R] [--out FILE] [workload ...]
 workloads: cfg4 (the cfg4_llama_r2_bf16 shapes, rank 2, one iteration; no uncompressed tensor) and
 resnet50 (ResNet-50 shapes, rank 2, two iterations, bf16; its 1-D tensors are the flat tail); cfg4
 by default."""
@@ -39,6 +39,8 @@ def quartiles(xs):
 
 
 def run(name, w, a, rank_id):
+    if a.rank is not None:
+        w = dict(w, rank=a.rank)
     from powersgd_amd import Config, Fp32ResidualPowerSGD
 
     dev = torch.device("cuda:0")
@@ -118,6 +120,7 @@ def main():
     ap.add_argument("--world", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--rank", type=int, default=None, help="the workloads at this rank instead of their own")
     ap.add_argument("--out", default=None)
     ap.add_argument("workloads", nargs="*", default=["cfg4"])
     a = ap.parse_args()

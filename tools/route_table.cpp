@@ -59,8 +59,10 @@ int main() {
     std::printf("| caller | rank bucket | I | step parity | launches (`;` ends an iteration, `=>` the output pass) |\n");
     std::printf("|---|---|---|---|---|\n");
     for (const Caller& who : callers)
-        for (int R : {1, 2, 4, 8}) {
-            if (who.mix && R == 8) continue;  // mixed instances: rank buckets 1 / 2 / 4
+        for (int R : {1, 2, 4, 8, 16}) {
+            // mixed instances: rank buckets 1 / 2 / 4 and 16 / 32, not 8; the other callers' rows of
+            // bucket 8 stand for 8-32
+            if (who.mix ? R == 8 : R == 16) continue;
             for (int I = 1; I <= 4; ++I) {
                 psgd_plan p;
                 p.rbucket = R;
@@ -71,7 +73,7 @@ int main() {
                 p.oe_ok = R == 1 && I >= 3;
                 p.qfold_ok = R == 2 || R == 4;
                 const std::string a = step_launches(p, who, 0), b = step_launches(p, who, 1);
-                const char* rb = R == 8 ? "8-32" : R == 1 ? "1" : R == 2 ? "2" : "4";
+                const char* rb = R == 16 ? "16-32" : R == 8 ? "8-32" : R == 1 ? "1" : R == 2 ? "2" : "4";
                 if (a == b) {
                     std::printf("| %s | %s | %d | any | %s |\n", who.name, rb, I, a.c_str());
                 } else {

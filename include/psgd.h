@@ -27,6 +27,8 @@
  *                          the reference gets from autograd's accumulation into p.grad
  *                          (README.md:39-42, powersgd/__init__.py:24-25) and the per-bucket
  *                          gather of the averaged gradients (paper-code/train_pytorch.py:106-131)
+ *   psgd_clip_outputs      torch.nn.utils.clip_grad_norm_ on what a step returned, from the
+ *                          low-rank factors where the plan has them (no reference counterpart)
  *
  * Conventions
  *  - No torch types. Device buffers are plain pointers on the plan's device; `stream` is a
@@ -597,6 +599,46 @@ int psgd_aggregate_comm_dst(psgd_plan* plan, void* const* grads, void* const* ds
 int psgd_aggregate_ipc_dst(psgd_plan* plan, void* const* grads, void* const* dst, int64_t step,
                            psgd_flat* flat, void* const* unc, void* const* unc_dst, void* stream);
 int psgd_plan_dst_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
+
+/* ------------------------ global-norm clipping of a step's averages (clip_grad_norm_) ---------- */
+/* torch.nn.utils.clip_grad_norm_ (L2) over everything a step returned, on the stream, with no host
+ * synchronisation: norm = sqrt(sum of squares of the compressed averages `out` and of the dense
+ * uncompressed averages `flat_out`), coef = min(1, max_norm / (norm + 1e-6)), and, when coef < 1,
+ * every element x <- x * float(coef) (bf16: bf16(float(x) * float(coef)), round to nearest even;
+ * fp64: x * coef). All sums are fp64 in a fixed order: the same inputs give the same bits.
+ *   `out`       the compressed averages of `step` (the output buffer the step wrote; the plan's
+ *               dtype, psgd_plan_output_numel elements); NULL: none (a warm-up step)
+ *   `flat_out`  the dense uncompressed averages (the plan's dtype), flat_numel elements; NULL / 0: none
+ *   `max_norm`  > 0; +inf: the norm only, no scale launch. <= 0 or NaN: PSGD_ERR_VALUE
+ *   `result`    device, 2 doubles, 8-byte aligned: norm, coef. A non-finite norm gives coef = NaN
+ *               and leaves every output untouched. The scale pass reads coef from here on the
+ *               device; its workgroups return at once when coef >= 1
+ *   `form`      how the compressed tensors' sum of squares is formed:
+ *     1 factors a compressed tensor's average is A = alpha sum_k P_k Q_k^T over the term set the
+ *               step's output pass read; with the terms stacked, P^ = [P_0 .. P_{I-1}] and Q^
+ *               likewise, ||A||_F^2 = alpha^2 <P^^T P^, Q^^T Q^>_F exactly (the cross blocks
+ *               between iterations included): two small fp64 Gram matrices per matrix, read from
+ *               the factors; the n x m output is never read. The plan records the term set when a
+ *               whole-plan output pass runs (psgd_decompress, every psgd_aggregate* form); the call
+ *               must follow the aggregate / decompress of `step` at world size `world` on the same
+ *               stream, before the plan's next psgd_compress. Refused before any launch where it
+ *               does not apply: a wide plan (ranks above 32), an fp64 plan, num_iters_per_step x
+ *               rank bucket > 64, or `out` NULL: PSGD_ERR_VALUE; no record of (`step`, `world`)
+ *               (never run, run per bucket, the next step already started, the plan re-bound):
+ *               PSGD_ERR_STATE.
+ *     2 stream  a sum of squares over `out` (one read of the outputs).
+ *     0 auto    factors where they apply, else stream (psgd_plan_norm_form reports which;
+ *               PSGD_NORM_FORM=auto|factors|stream, read at psgd_plan_create, overrides the choice
+ *               for A/B runs, the factor form still only where it applies).
+ * `flat_out` always takes the stream form. The first call makes one device allocation owned by the
+ * plan (work items, Gram partials, per-workgroup partials), freed with it; the caller's workspace
+ * layout is untouched. An unbound plan: PSGD_ERR_STATE; a buffer not aligned to its element size
+ * (`result`: 8 bytes): PSGD_ERR_LAYOUT.
+ * psgd_plan_norm_form: the form auto takes for (`step`, `world`): 1 or 2. On an unbound plan the
+ * answer is the plan's own (no step has run: 1 wherever the factor form can apply). */
+int psgd_clip_outputs(psgd_plan* plan, int64_t step, int32_t world, void* out, void* flat_out,
+                      int64_t flat_numel, double max_norm, int32_t form, double* result, void* stream);
+int psgd_plan_norm_form(const psgd_plan* plan, int64_t step, int32_t world, int32_t* form);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,9 @@ __all__ = ["Aggregator", "AllReduce", "Config", "Fp32ResidualPowerSGD", "PowerSG
 def optimizer_step(optimizer: torch.optim.Optimizer, aggregator: Aggregator):
     """Aggregate gradients across workers with ``aggregator``, then take an optimizer
     step with the aggregate; afterwards ``p.grad`` holds the error-feedback buffer
-    (reference powersgd/__init__.py:7-25)."""
+    (reference powersgd/__init__.py:7-25). Global-norm clipping of the aggregate goes through the
+    aggregator: ``PowerSGD(..., max_grad_norm=x)`` or its ``max_grad_norm`` attribute (the caller
+    has no point between the aggregate and the step at which to clip)."""
     params = params_in_optimizer(optimizer)
     grads = [p.grad.data for p in params]  # type: ignore
     avg_grads = aggregator.aggregate(grads)  # subtracts the approximation from grads

@@ -92,6 +92,8 @@ _SIGNATURES = {
     "psgd_aggregate_comm_dst": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_aggregate_ipc_dst": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
     "psgd_plan_dst_ok": ([_vp, _i64, _i32, _P_i32], _i32),
+    "psgd_clip_outputs": ([_vp, _i64, _i32, _vp, _vp, _i64, _dbl, _i32, _vp, _vp], _i32),
+    "psgd_plan_norm_form": ([_vp, _i64, _i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -302,6 +304,25 @@ class Plan:
         """psgd_aggregate_ipc_dst: the same over the plan's open exchange session (``aggregate_ipc``)."""
         check(lib().psgd_aggregate_ipc_dst(self._h, grads, dst, step, flat._h if flat is not None else None, unc,
                                            unc_dst, stream))
+
+    # --- global-norm clipping of a step's averages
+    NORM_AUTO, NORM_FACTORS, NORM_STREAM = 0, 1, 2
+
+    def norm_form(self, step: int, world: int = 1) -> int:
+        """The form ``clip_outputs`` takes under ``form=NORM_AUTO`` for ``step`` at world size ``world``
+        (psgd_plan_norm_form): ``NORM_FACTORS`` (the norm from the low-rank factors) or ``NORM_STREAM``
+        (a sum of squares over the outputs). On an unbound plan: the plan's own answer."""
+        f = _i32()
+        check(lib().psgd_plan_norm_form(self._h, step, world, ctypes.byref(f)))
+        return int(f.value)
+
+    def clip_outputs(self, step: int, world: int, out_ptr: int, flat_ptr: int, flat_numel: int, max_norm: float,
+                     result_ptr: int, stream: int, form: int = 0) -> None:
+        """psgd_clip_outputs: clip the averages ``step`` returned (compressed slab ``out_ptr``, dense
+        uncompressed slab ``flat_ptr``; 0: none) by their global L2 norm, stream-ordered. ``result_ptr``:
+        two device doubles (norm, coef). ``max_norm = inf``: the norm only."""
+        check(lib().psgd_clip_outputs(self._h, step, world, out_ptr or None, flat_ptr or None, flat_numel,
+                                      float(max_norm), form, result_ptr, stream))
 
     # --- buckets of shape groups (W > 1 comm/compute overlap)
     def set_buckets(self, group_end: Sequence[int]) -> None:

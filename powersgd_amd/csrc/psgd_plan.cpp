@@ -48,6 +48,7 @@ psgd_plan::~psgd_plan() {
     ipc_release(this);
     mixed_release(this);
     direct_release(this);
+    norm_release(this);
     if (xerr_host) (void)hipHostFree(xerr_host);
     if (stamp_buf) (void)hipFree(stamp_buf);
 }
@@ -179,6 +180,14 @@ int psgd_plan_create(const int64_t* dims, const int32_t* ndims, int32_t num_tens
     p->oe_on = env_int("PSGD_OE", 1) != 0;
     p->orth_chol = env_int("PSGD_ORTH_CHOL", 1) != 0;
     p->mix_ingest_on = env_int("PSGD_MIXED_INGEST", 1) != 0;
+    // PSGD_NORM_FORM=auto|factors|stream: the form psgd_clip_outputs' auto takes (A/B runs); the
+    // factor form still runs only where it applies
+    if (const char* nf = std::getenv("PSGD_NORM_FORM")) {
+        const std::string v(nf);
+        if (v == "factors") p->norm_env = 1;
+        else if (v == "stream") p->norm_env = 2;
+        else if (!v.empty() && v != "auto") return fail(PSGD_ERR_VALUE, "PSGD_NORM_FORM must be auto, factors or stream");
+    }
 
     // output layout: dense, tensor order (what torch.cat / unflatten produce); a matrix
     // whose segment is not 16-byte aligned takes the scalar path
@@ -205,7 +214,13 @@ int psgd_plan_create(const int64_t* dims, const int32_t* ndims, int32_t num_tens
             md.tensor = g.tensors[b];
             md.group = int(gi);
             p->mats.push_back(md);
-            p->base_vec.push_back((dtype != PSGD_F64 && g.m % 4 == 0 && g.r <= 8 && md.out_off % 4 == 0) ? 1 : 0);
+            // rank buckets 16 / 32: k_even's and k_apply's instances know the scalar (V = 1) layout
+            // alone, for every matrix of the plan, also one whose own rank is capped at 8 or less by
+            // its rows or columns (a [3, 200] matrix: with the vector layout its even product and
+            // apply tiles covered a quarter of each strip and the rest was never written)
+            const bool bucket_vec = p->rbucket <= 8 || p->rbucket > 32;
+            p->base_vec.push_back(
+                (dtype != PSGD_F64 && g.m % 4 == 0 && g.r <= 8 && bucket_vec && md.out_off % 4 == 0) ? 1 : 0);
         }
         poff += int64_t(g.tensors.size()) * g.n * g.r;
         qoff += int64_t(g.tensors.size()) * g.m * g.r;
@@ -300,6 +315,7 @@ int psgd_plan_bind(psgd_plan* p, int32_t device, void* P, void* Q, void* workspa
     p->P = static_cast<float*>(P);  // fp64 plans: double buffers (see P64/Q64)
     p->Q = static_cast<float*>(Q);
     p->ws = static_cast<char*>(workspace);
+    p->norm_rec.have = false;  // a recorded term set names the buffers of the previous binding
     const size_t nt = p->shapes.size();
     p->grad_tab.bind(p->dev<char>(p->o_ptrs), nt);
     p->rdst_tab.bind(p->dev<char>(p->o_rdst), nt);

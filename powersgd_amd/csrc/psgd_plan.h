@@ -5,6 +5,7 @@
 //                      functions shared with admission, and the reducer building blocks
 //   psgd_mixed.cpp     psgd_aggregate_mixed[_comm]: admission of the mixed instances, fold queries
 //   psgd_direct.cpp    psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst: admission, state, entry points
+//   psgd_norm.cpp      psgd_clip_outputs / psgd_plan_norm_form: form choice, state, launches
 //   psgd_ipc.cpp       the IPC exchange arena and psgd_aggregate_ipc
 //   psgd_flat.cpp      flat pack and DDP run tables
 //   psgd_comm.cpp      the communicator behind psgd_aggregate_comm
@@ -413,6 +414,32 @@ struct psgd_plan {
         size_t stage_cap = 0;  // floats
     };
     Direct* direct = nullptr;
+    // psgd_clip_outputs (psgd_norm.cpp). The record: the term set the output pass of `step` read at
+    // world size `world` (ApplyArgs::apx and alpha), written where that set is built
+    // (decompress_impl; final_stage on steps whose fused final pass wrote the output) and
+    // dropped when the next step's first iteration starts, so the norm entry never re-derives a
+    // route. Bucket calls (a span) leave none. `norm`: device state of its own like Mixed and
+    // Direct (work items, Gram partials, per-tensor squares, stream partials), made by the first
+    // psgd_clip_outputs call; nothing of it lives in the caller's workspace.
+    struct NormRec {
+        bool have = false;
+        int64_t step = -1;
+        int32_t world = 0, nterms = 0;
+        float alpha = 0.f;
+        Terms apx{};
+    };
+    NormRec norm_rec;
+    void record_terms(int64_t step, int32_t world, const Terms& apx, int nterms, float alpha) {
+        norm_rec.have = true;
+        norm_rec.step = step;
+        norm_rec.world = world;
+        norm_rec.nterms = nterms;
+        norm_rec.alpha = alpha;
+        norm_rec.apx = apx;
+    }
+    int norm_env = 0;  // PSGD_NORM_FORM, read at create: 0 auto, 1 factors, 2 stream (A/B runs)
+    struct Norm;
+    Norm* norm = nullptr;
     int64_t xslot_off(int64_t step, int it) const {  // byte offset of a slot in every buffer
         return kXchgHeader + ((step & 1) * iters + it) * ipc_slot * int64_t(sizeof(float));
     }
@@ -640,6 +667,8 @@ int aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step,
 void mixed_release(psgd_plan* p);
 // psgd_direct.cpp: frees the plan's direct-store state
 void direct_release(psgd_plan* p);
+// psgd_norm.cpp: frees the plan's norm state
+void norm_release(psgd_plan* p);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
 int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
 // psgd_step.cpp: the world-size-W step of psgd_aggregate_comm; with `mix`, of psgd_aggregate_mixed_comm;

@@ -403,6 +403,15 @@ int final_stage(const Iter& i) {
     fa.ntiles = fr[1] - fr[0];
     if (c.fl && c.write_out) fa.flat = *c.fl;  // uncompressed tensors ride in the same launch
     if (fa.ntiles + fa.flat.nitems == 0) return PSGD_OK;
+    if (c.write_out && c.span == nullptr) {
+        // this pass writes the output (world size 1): the terms psgd_clip_outputs reads afterwards
+        // are the local ones, history slots 0 / 1 and this iteration's P in the state buffer (the
+        // projection form's output G0 X X^T is P0 Q0^T + P1 X^T with P1 = G0 X - P0 R'^T, the state)
+        Terms apx;
+        fill_terms(p, i.step, p->iters, apx, [p](int k) { return p->hist(0, k); },
+                   [&](int k) { return k + 1 < p->iters ? p->hist(1, k) : i.out(); });
+        p->record_terms(i.step, 1, apx, p->iters, 1.f);
+    }
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     if (int st = timing_begin(p, i.s, &ev, true)) return st;  // benchmark timing: the final pass
     TimedScope ts(ev);
@@ -539,6 +548,7 @@ hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArg
 }
 
 int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s, StepCtx c) {
+    if (it == 0) p->norm_rec.have = false;  // a new step: the recorded output terms are about to be overwritten
     if (p->f64()) return compress_f64(p, grads, step, it, s);
     if (p->wide()) return compress_wide(p, grads, step, it, s, c.xout);
     if (int st = refresh_pointers(p, grads, s)) return st;
@@ -584,6 +594,9 @@ int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t s
     aa.ntiles = nt;
     if (c.fl && o.flat) aa.flat = *c.fl;  // uncompressed tensors (mixed_comm: their round items) ride in the launch
     if (nt + aa.flat.nitems == 0) return PSGD_OK;
+    // for psgd_clip_outputs: the term set this pass reads (world size 1: the shared instance reads the
+    // local terms alone, history slots 0 / 1, and never the state buffer)
+    if (c.span == nullptr) p->record_terms(step, world, o.shared ? aa.res : aa.apx, I, aa.alpha);
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     if (o.timed)
         if (int st = timing_begin(p, s, &ev, true)) return st;

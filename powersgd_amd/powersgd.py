@@ -82,6 +82,16 @@ def _output_slab(shapes, code: int, dev_index: int):
     return _psgd_host.OutputSlab([list(s) for s in shapes], code, dev_index)
 
 
+def _check_max_grad_norm(value: Optional[float]) -> Optional[float]:
+    """``max_grad_norm`` as a float: positive (``inf``: measure the norm, never scale) or None."""
+    if value is None:
+        return None
+    value = float(value)
+    if not value > 0.0:  # 0, negatives and NaN
+        raise ValueError(f"max_grad_norm must be a positive number or None, got {value}")
+    return value
+
+
 class Aggregator(ABC):
     """reference :11-19."""
 
@@ -100,6 +110,7 @@ class AllReduce(Aggregator):
 
     def __init__(self):
         self._plans: Dict[tuple, "_FlatEntry"] = {}
+        self._last: Optional["_FlatEntry"] = None  # the entry whose slab the latest call returned
 
     def aggregate(self, gradients: List[torch.Tensor]) -> List[torch.Tensor]:
         if len(gradients) == 0:
@@ -112,6 +123,7 @@ class AllReduce(Aggregator):
         if entry is None:
             entry = self._plans[key] = _FlatEntry([g.shape for g in gradients], code, g0.dtype, g0.device)
         _psgd_host.fill_list(gradients, entry.ptr_addr, code, dev_index)
+        self._last = entry
         return entry.run(entry.ptr_addr)
 
 
@@ -150,10 +162,25 @@ class Config(NamedTuple):
 
 class PowerSGD(Aggregator):
     """Applies PowerSGD only after a configurable number of steps, and only on
-    parameters with strong compression (reference :41-105)."""
+    parameters with strong compression (reference :41-105).
 
-    def __init__(self, params: List[torch.Tensor], config: Config):
+    ``max_grad_norm`` (keyword; also a settable attribute; not in the reference): clip what
+    ``aggregate`` is about to return by its global L2 norm, as ``torch.nn.utils.clip_grad_norm_``
+    would on the returned tensors (``coef = min(1, max_grad_norm / (norm + 1e-6))``), inside the
+    library and without a host synchronisation (psgd_clip_outputs): on a compressing step the norm
+    of the compressed averages comes from the low-rank factors where the plan allows, so a step
+    whose norm is below the threshold never re-reads its outputs. ``last_grad_norm`` and
+    ``last_clip_coef`` are 0-dim float64 device tensors, views of one result buffer that the next
+    call overwrites. The gradients still become the residual; clipping never touches it. ``None``
+    (default): every code path is the unclipped one."""
+
+    def __init__(self, params: List[torch.Tensor], config: Config, *, max_grad_norm: Optional[float] = None):
         self.config = config
+        self._max_grad_norm: Optional[float] = None
+        self.max_grad_norm = max_grad_norm
+        self._clip_result: Optional[torch.Tensor] = None
+        self.last_grad_norm: Optional[torch.Tensor] = None
+        self.last_clip_coef: Optional[torch.Tensor] = None
         self.device = list(params)[0].device
         self.is_compressed_mask = [self._should_compress(p.shape) for p in params]
         self.step_counter = 0
@@ -179,10 +206,40 @@ class PowerSGD(Aggregator):
             self._order.append(ic if c else iu)
             ic, iu = (ic + 1, iu) if c else (ic, iu + 1)
 
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value: Optional[float]) -> None:
+        self._max_grad_norm = _check_max_grad_norm(value)
+
+    def _clip(self, out_ptr: int, flat_ptr: int, flat_numel: int) -> None:
+        """Clip the averages the step just enqueued (compressed slab, dense uncompressed slab) on
+        the codec's stream; norm and coefficient stay on the device."""
+        codec = self._powersgd
+        if self._clip_result is None:
+            self._clip_result = torch.zeros(2, dtype=torch.float64, device=self.device)
+            self.last_grad_norm, self.last_clip_coef = self._clip_result[0], self._clip_result[1]
+        world = 1
+        if is_distributed():  # the world size the step's output pass ran at
+            world = codec._comm.world if codec._comm else torch.distributed.get_world_size()
+        # the step whose outputs these are: the codec's counter has already moved on
+        step = codec.step_counter - 1 if out_ptr else 0
+        codec._plan.clip_outputs(step, world, out_ptr, flat_ptr, flat_numel, self._max_grad_norm,
+                                 self._clip_result.data_ptr(), _stream(self.device))
+
     def aggregate(self, gradients: List[torch.Tensor]) -> List[torch.Tensor]:
         self.step_counter += 1
         if self.step_counter <= self.config.start_compressing_after_num_steps:
-            return self._allreduce.aggregate(gradients)
+            outs = self._allreduce.aggregate(gradients)
+            if self._max_grad_norm is not None and len(outs) > 0:
+                entry = self._allreduce._last
+                if entry.dtype != self._powersgd.dtype:
+                    raise RuntimeError(f"max_grad_norm: gradients are {entry.dtype}, the codec's are "
+                                       f"{self._powersgd.dtype}")
+                self._clip(0, entry.slab.data_ptr(), entry.numel)
+            return outs
         if not isinstance(gradients, list):
             gradients = list(gradients)
         self._table.fill(gradients)  # reference _split :76-84 + the checks its torch ops make
@@ -216,6 +273,10 @@ class PowerSGD(Aggregator):
             outs = self._powersgd._aggregate_table(self._table.comp_addr())
             if self._unc is not None:
                 outs = outs + self._unc.run(self._table.unc_addr())
+        if self._max_grad_norm is not None:
+            u = self._unc
+            self._clip(codec._slab.data_ptr(), u.slab.data_ptr() if u is not None else 0,
+                       u.numel if u is not None else 0)
         return [outs[i] for i in self._order]  # reference _merge :86-99
 
     def close(self) -> None:

@@ -32,20 +32,37 @@ without the IPC exchange, an ineligible plan) runs it.
 from __future__ import annotations
 
 import ctypes
-from typing import List
+from abc import ABCMeta
+from typing import List, Optional
 
 import torch
 
 from . import _lib
-from .powersgd import Aggregator, Config, PowerSGD, _output_slab, _psgd_host, _require_device, _stream, _views
+from .powersgd import (Aggregator, Config, PowerSGD, _check_max_grad_norm, _output_slab, _psgd_host,
+                       _require_device, _stream, _views)
 from .utils import is_distributed
 
 
-class Fp32ResidualPowerSGD(Aggregator):
+class _ClipKeyword(ABCMeta):
+    """``Fp32ResidualPowerSGD(params, config, fused=False, max_grad_norm=None)``: the keyword is taken
+    at the class call, checked before any device work, and handed to the inner fp32 aggregator once
+    it exists. ``__init__`` keeps the parameter list ``(params, config, fused)`` that existing callers
+    and tests inspect."""
+
+    def __call__(cls, *args, max_grad_norm: Optional[float] = None, **kwargs):
+        max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        obj = super().__call__(*args, **kwargs)
+        obj.inner.max_grad_norm = max_grad_norm
+        return obj
+
+
+class Fp32ResidualPowerSGD(Aggregator, metaclass=_ClipKeyword):
     """``PowerSGD(params, config)`` for bfloat16 ``params`` on one GPU per process, with an fp32
     residual owned by the aggregator: ``residual`` (flat), ``views`` (per parameter), ``inner``
     (the fp32 ``PowerSGD`` over ``views``). ``fused``: take the one-call fused step where it
-    applies (module docstring); same results, bit for bit."""
+    applies (module docstring); same results, bit for bit. ``max_grad_norm`` (keyword, also a
+    settable attribute): global-norm clipping by the inner aggregator (``PowerSGD.max_grad_norm``):
+    the fp32 averages are clipped before the GATHER rounds them to bf16."""
 
     def __init__(self, params: List[torch.Tensor], config: Config, fused: bool = False):
         params = list(params)
@@ -89,6 +106,25 @@ class Fp32ResidualPowerSGD(Aggregator):
     def is_compressed_mask(self) -> List[bool]:
         return self.inner.is_compressed_mask
 
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        """``PowerSGD.max_grad_norm`` of ``inner`` (settable). With a value the step runs the three
+        stages even under ``fused=True``: the one-call forms store bf16 averages, and the clip
+        belongs before that rounding."""
+        return self.inner.max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value: Optional[float]) -> None:
+        self.inner.max_grad_norm = value
+
+    @property
+    def last_grad_norm(self):
+        return self.inner.last_grad_norm
+
+    @property
+    def last_clip_coef(self):
+        return self.inner.last_clip_coef
+
     def aggregate(self, gradients: List[torch.Tensor]) -> List[torch.Tensor]:
         """Average ``gradients`` (bf16) across workers; zeroes them (they are folded into the fp32
         residual, which keeps the compression error)."""
@@ -128,6 +164,8 @@ class Fp32ResidualPowerSGD(Aggregator):
         psgd_aggregate_mixed_comm in a process group that runs over the library's communicator,
         psgd_aggregate_mixed_ipc in one that runs over the IPC exchange."""
         inner = self.inner
+        if inner.max_grad_norm is not None:  # clipped before the bf16 rounding: the three stages
+            return False
         if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
             return False
         plan = inner._powersgd._plan

@@ -29,6 +29,8 @@
  *                          gather of the averaged gradients (paper-code/train_pytorch.py:106-131)
  *   psgd_clip_outputs      torch.nn.utils.clip_grad_norm_ on what a step returned, from the
  *                          low-rank factors where the plan has them (no reference counterpart)
+ *   psgd_clip_dst          the same after a direct-store completion: the averages scaled where
+ *                          they lie, inside the DDP buckets
  *
  * Conventions
  *  - No torch types. Device buffers are plain pointers on the plan's device; `stream` is a
@@ -639,6 +641,42 @@ int psgd_plan_dst_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t
 int psgd_clip_outputs(psgd_plan* plan, int64_t step, int32_t world, void* out, void* flat_out,
                       int64_t flat_numel, double max_norm, int32_t form, double* result, void* stream);
 int psgd_plan_norm_form(const psgd_plan* plan, int64_t step, int32_t world, int32_t* form);
+
+/* psgd_clip_dst: psgd_clip_outputs for the direct-store completion (psgd_aggregate_comm_dst /
+ * psgd_aggregate_ipc_dst), whose averages lie at per-tensor destinations and in no slab. Called
+ * right after that step on the same stream with the same `dst`, `flat` and `unc_dst`. DEFINED as,
+ * and bit for bit equal to (result[0..1], every destination element, nothing outside the
+ * destinations' numel elements), this sequence, which is never run:
+ *   1. copy every dst[i] / unc_dst[k] into a dense output slab (the plan's output offsets) / a
+ *      dense flat slab (the flat plan's order), each the base of an allocation of its own
+ *   2. psgd_clip_outputs(plan, step, world, out, flat_out, flat->total, max_norm, form = 1, result)
+ *   3. copy back
+ * Why the bits agree. Compressed tensors: the factor form reads the plan's recorded term set,
+ * which the destination-table output pass records exactly as the slab one does; the n x m
+ * averages are never read, so where they lie does not matter. Uncompressed tensors: the stream sum
+ * runs over the plan's own fp32 staging buffer (flat->total floats), which still holds the sums
+ * that the step's copy items wrote to unc_dst, in the flat plan's layout. That buffer is the base
+ * of an allocation, like the flat slab of step 1, so the sum's split into head, 16-byte vectors
+ * and tail and its workgroup partition (functions of the base's alignment and the length alone)
+ * are the same, and so is every partial sum. The scale is element-wise (x * float(coef)), so its
+ * partition cannot show. There is no stream form for the compressed tensors: a sum over scattered
+ * destinations would partition differently from the slab's.
+ * The scale pass (k_norm_scale_dst, fp32) goes through the two destination tables in work items
+ * built once per plan / flat plan from the numels; a destination needs 4-byte alignment only (an
+ * item splits into a head of 0-3 elements, 16-byte vectors and a tail by its pointer). Its
+ * workgroups return at once, writing nothing, unless coef < 1 and the norm is finite.
+ * max_norm = +inf: the norm only, no scale launch.
+ * psgd_plan_clip_dst_ok: *ok = 1 exactly when the plan is one psgd_plan_dst_ok can serve by shape
+ * (PSGD_F32, not wide, one bucket), num_iters_per_step x rank bucket <= 64, and PSGD_NORM_FORM does
+ * not force the stream form. No device is asked.
+ * Refusals, all before any launch: a null plan / dst / result, a flat plan with total > 0 and a
+ * null unc_dst or a null entry, max_norm <= 0 or NaN, a plan for which psgd_plan_clip_dst_ok is 0:
+ * PSGD_ERR_VALUE; a destination that is not 4-byte aligned, `result` not 8-byte aligned:
+ * PSGD_ERR_LAYOUT; an unbound plan, no record of (`step`, `world`), a flat tail with no staging of
+ * at least flat->total floats from a preceding direct-store call: PSGD_ERR_STATE. */
+int psgd_clip_dst(psgd_plan* plan, int64_t step, int32_t world, void* const* dst, psgd_flat* flat,
+                  void* const* unc_dst, double max_norm, double* result, void* stream);
+int psgd_plan_clip_dst_ok(const psgd_plan* plan, int32_t* ok);
 
 #ifdef __cplusplus
 }

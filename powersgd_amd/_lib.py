@@ -94,6 +94,8 @@ _SIGNATURES = {
     "psgd_plan_dst_ok": ([_vp, _i64, _i32, _P_i32], _i32),
     "psgd_clip_outputs": ([_vp, _i64, _i32, _vp, _vp, _i64, _dbl, _i32, _vp, _vp], _i32),
     "psgd_plan_norm_form": ([_vp, _i64, _i32, _P_i32], _i32),
+    "psgd_clip_dst": ([_vp, _i64, _i32, _vp, _vp, _vp, _dbl, _vp, _vp], _i32),
+    "psgd_plan_clip_dst_ok": ([_vp, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -323,6 +325,21 @@ class Plan:
         two device doubles (norm, coef). ``max_norm = inf``: the norm only."""
         check(lib().psgd_clip_outputs(self._h, step, world, out_ptr or None, flat_ptr or None, flat_numel,
                                       float(max_norm), form, result_ptr, stream))
+
+    def clip_dst_ok(self) -> int:
+        """1 where ``clip_dst`` serves this plan (psgd_plan_clip_dst_ok: a plan ``dst_ok`` can serve by
+        shape whose norm comes from the factors), else 0. Asks no device."""
+        ok = _i32()
+        check(lib().psgd_plan_clip_dst_ok(self._h, ctypes.byref(ok)))
+        return int(ok.value)
+
+    def clip_dst(self, step: int, world: int, dst, max_norm: float, result_ptr: int, stream: int, flat=None,
+                 unc_dst=None) -> None:
+        """psgd_clip_dst: ``clip_outputs`` (the factor form) on the averages ``aggregate_comm_dst`` /
+        ``aggregate_ipc_dst`` just stored at ``dst[i]`` / ``unc_dst[k]``, scaled in place there. Call
+        right after that step on the same stream with the same tables."""
+        check(lib().psgd_clip_dst(self._h, step, world, dst, flat._h if flat is not None else None, unc_dst,
+                                  float(max_norm), result_ptr, stream))
 
     # --- buckets of shape groups (W > 1 comm/compute overlap)
     def set_buckets(self, group_end: Sequence[int]) -> None:

@@ -151,6 +151,34 @@ int prepare(psgd_plan* p, void* const* grads, void* const* dst, psgd_flat* f, vo
 
 }  // namespace
 
+bool psgd::direct_shape_ok(const psgd_plan* p) {
+    int code = 0;
+    return ineligible(p, &code) == nullptr;
+}
+
+int psgd::direct_select(psgd_plan* p, void* const* dst, const psgd_flat* f, void* const* unc_dst, hipStream_t s,
+                        DirectDst* t) {
+    if (f) {  // checked before the state is made: a refusal leaves nothing behind
+        const psgd_plan::Direct* m = p->direct;
+        if (!m || !m->stage || m->stage_cap < size_t(f->total) || m->unc_cap < size_t(f->count))
+            return fail(PSGD_ERR_STATE, "the flat tail is not staged (call after psgd_aggregate_comm_dst / _ipc_dst)");
+    }
+    if (int st = ensure(p)) return st;
+    psgd_plan::Direct& m = *p->direct;
+    if (f) {
+        if (m.unc_dst.n != size_t(f->count)) {
+            PSGD_HIP(hipStreamSynchronize(s));
+            m.unc_dst.bind(m.unc_dev, size_t(f->count));
+        }
+        PSGD_HIP(m.unc_dst.select(unc_dst, s));
+        t->unc_dst = m.unc_dst.table();
+        t->stage = m.stage;
+    }
+    PSGD_HIP(m.dst.select(dst, s));
+    t->dst = m.dst.table();
+    return PSGD_OK;
+}
+
 void psgd::direct_release(psgd_plan* p) {
     if (!p->direct) return;
     psgd_plan::Direct* m = p->direct;

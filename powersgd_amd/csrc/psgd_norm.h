@@ -53,6 +53,23 @@ struct NormRangeArgs {
     int64_t numel[2];
     int32_t nwg[2];
 };
+// psgd_clip_dst: the scale pass through per-tensor destination tables (table 0: the plan's tensors,
+// table 1: the flat plan's). One work item = up to kNormDstItem consecutive elements of one
+// destination, starting at a multiple of kNormDstItem: the item's pointer has its destination's
+// alignment modulo 16 bytes. Built on the host from the numels alone.
+constexpr int kNormDstVecs = 8;                          // 16-byte vectors per thread of an item
+constexpr int kNormDstItem = kNormDstVecs * kBlock * 4;  // fp32 elements: half of k_norm_scale's workgroup
+static_assert(kNormDstItem % 4 == 0 && kNormDstItem <= kNormVecs * 4, "item length");
+struct NormDstItem {
+    int64_t off;          // elements from the destination's first
+    int32_t tensor, cnt;  // index into the item's table; elements (<= kNormDstItem)
+};
+// workgroups [0, nitems[0]) serve table 0's items, the next nitems[1] table 1's
+struct NormDstArgs {
+    const NormDstItem* items[2];
+    void* const* table[2];
+    int32_t nitems[2];
+};
 struct NormFinishArgs {
     const double* sq;     // factor form: per-tensor squares, nsq of them (tensor order); else null
     int32_t nsq;
@@ -71,6 +88,7 @@ hipError_t launch_norm_mat(const NormMatArgs& a, int nmats, hipStream_t s);
 hipError_t launch_norm_stream(int dtype, const NormRangeArgs& r, double* part, hipStream_t s);
 hipError_t launch_norm_finish(const NormFinishArgs& a, hipStream_t s);
 hipError_t launch_norm_scale(int dtype, const NormRangeArgs& r, const double* result, hipStream_t s);
+hipError_t launch_norm_scale_dst(const NormDstArgs& a, const double* result, hipStream_t s);  // fp32
 // resident waves per SIMD of every instance (0: scratch), for the admission check and tools
 int norm_min_waves();
 

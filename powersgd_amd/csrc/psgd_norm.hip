@@ -1,7 +1,8 @@
 // Kernels of psgd_clip_outputs (psgd_norm.h): the global L2 norm of a step's averages from the
 // low-rank factors (k_norm_gram, k_norm_mat) or from the dense outputs (k_norm_stream), the
 // finishing step (k_norm_finish: norm and clip coefficient, device-side) and the scale pass
-// (k_norm_scale), which exits at once when nothing is clipped.
+// (k_norm_scale; k_norm_scale_dst of psgd_clip_dst: through per-tensor destination tables), which
+// exits at once when nothing is clipped.
 //
 // Codegen rules as everywhere in the codec: global pointers in address space
 // 1 or buffer descriptors, unconditional loads from clamped addresses masked by selects, every
@@ -353,6 +354,54 @@ __global__ __launch_bounds__(kBlock) void k_norm_scale(NormRangeArgs r, const do
     }
 }
 
+// ---------------------------------------------------------------- scale, destination tables
+// psgd_clip_dst: x <- x * float(coef) through two tables of per-tensor destinations (fp32 views
+// inside DDP buckets: 4-byte aligned, no better in general), one NormDstItem per workgroup; the
+// same early return as k_norm_scale. The item's pointer decides its split once: a head of 0-3
+// elements up to the first 16-byte boundary, 16-byte vectors, a tail of 0-3 elements. Every load
+// (kNormDstVecs vectors per thread through a descriptor that spans the item's own vectors, clamped
+// offsets; one head / tail element per thread from a clamped address-space-1 address) is issued
+// before the first store; vector stores go through the same descriptor, element stores through
+// one-element descriptors, both write-through (PSGD_ST_AUX). Nothing outside the item's `cnt`
+// elements is read or written.
+__global__ __launch_bounds__(kBlock) void k_norm_scale_dst(NormDstArgs a, const double* result) {
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+    const gptr<const double> res = gconst<double>(result);
+    const double norm = res[0], coef = res[1];
+    if (!(coef < 1.0) || !isfinite(norm)) return;
+    const float c32 = float(coef);
+    const int which = int(blockIdx.x) < a.nitems[0] ? 0 : 1;
+    const NormDstItem it = a.items[which][int(blockIdx.x) - (which ? a.nitems[0] : 0)];
+    float* p = static_cast<float*>(a.table[which][it.tensor]) + it.off;
+    const int mis = int((reinterpret_cast<uintptr_t>(p) & 15) >> 2);
+    int head = mis ? 4 - mis : 0;
+    if (head > it.cnt) head = it.cnt;
+    const int nvec = (it.cnt - head) >> 2, tail = it.cnt - head - 4 * nvec;
+    const rsrc_t rv = make_rsrc(p + head, uint32_t(nvec) * 16u);
+    const int tid = int(threadIdx.x);
+    v4u x[kNormDstVecs];
+#pragma unroll
+    for (int q = 0; q < kNormDstVecs; ++q) {
+        const int i = q * kBlock + tid;
+        const int c = i < nvec ? i : nvec > 0 ? nvec - 1 : 0;  // clamped, unconditional (no vectors: reads 0)
+        x[q] = __builtin_amdgcn_raw_buffer_load_b128(rv, uint32_t(c) * 16u, 0, 0);
+    }
+    // head and tail: at most 6 elements, one per thread
+    const int ns = head + tail;
+    const int ei = tid < head ? tid : it.cnt - tail + (tid - head);
+    const float e = gconst<float>(p)[tid < ns ? ei : 0];
+#pragma unroll
+    for (int q = 0; q < kNormDstVecs; ++q) {
+        const int i = q * kBlock + tid;
+        const v4f y = __builtin_bit_cast(v4f, x[q]) * c32;
+        if (i < nvec) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, y), rv, uint32_t(i) * 16u, 0, PSGD_ST_AUX);
+    }
+    if (tid < ns) {
+        const rsrc_t re = make_rsrc(p + ei, 4u);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e * c32), re, 0, 0, PSGD_ST_AUX);
+    }
+}
+
 // ---------------------------------------------------------------- launchers
 hipError_t launch_norm_gram(int ept, const NormGramArgs& a, int nitems, int dtype, const NormRangeArgs& rg,
                             double* spart, hipStream_t s) {
@@ -404,6 +453,13 @@ hipError_t launch_norm_scale(int dtype, const NormRangeArgs& r, const double* re
     return hipGetLastError();
 }
 
+hipError_t launch_norm_scale_dst(const NormDstArgs& a, const double* result, hipStream_t s) {
+    const int n = a.nitems[0] + a.nitems[1];
+    if (n == 0) return hipSuccess;
+    k_norm_scale_dst<<<n, kBlock, 0, s>>>(a, result);
+    return hipGetLastError();
+}
+
 namespace {
 template <typename K>
 int kernel_waves(K k) {
@@ -429,6 +485,7 @@ int norm_min_waves() {
     w = std::min(w, kernel_waves(k_norm_scale<float>));
     w = std::min(w, kernel_waves(k_norm_scale<bf16_t>));
     w = std::min(w, kernel_waves(k_norm_scale<double>));
+    w = std::min(w, kernel_waves(k_norm_scale_dst));
     return w;
 }
 

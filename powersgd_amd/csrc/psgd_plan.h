@@ -667,6 +667,13 @@ int aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step,
 void mixed_release(psgd_plan* p);
 // psgd_direct.cpp: frees the plan's direct-store state
 void direct_release(psgd_plan* p);
+// psgd_direct.cpp, for psgd_clip_dst (psgd_norm.cpp): the plan is one the direct-store calls serve
+// by shape (fp32, not wide, one bucket); and the device tables of `dst` / `unc_dst` (the slots the
+// preceding direct-store call selected: no upload then) with the staged flat tail. A flat plan
+// whose tail the plan has not staged (no preceding direct-store call with at least f->total
+// floats): PSGD_ERR_STATE. Nothing is launched.
+bool direct_shape_ok(const psgd_plan* p);
+int direct_select(psgd_plan* p, void* const* dst, const psgd_flat* f, void* const* unc_dst, hipStream_t s, DirectDst* t);
 // psgd_norm.cpp: frees the plan's norm state
 void norm_release(psgd_plan* p);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`

@@ -40,7 +40,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .powersgd import Config, PowerSGD, _DTYPES, _psgd_host, _require_device, _stream
+from .powersgd import Config, PowerSGD, _DTYPES, _check_max_grad_norm, _psgd_host, _require_device, _stream
 from .utils import is_distributed
 
 
@@ -61,7 +61,20 @@ class _BucketRuns:
         self.runs.bind(dev_index, self.ws.data_ptr())
 
 
-class PowerSGDState:
+class _ClipKeyword(type):
+    """``PowerSGDState(config, params, ..., fused=False, max_grad_norm=None)``: the keyword is taken at
+    the class call, checked before any device work, and handed to the inner aggregator once it
+    exists (as ``Fp32ResidualPowerSGD`` takes it). ``__init__`` keeps the parameter list ``(config,
+    params, process_group, residual_dtype, fused)`` that existing callers and tests inspect."""
+
+    def __call__(cls, *args, max_grad_norm: Optional[float] = None, **kwargs):
+        max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        obj = super().__call__(*args, **kwargs)
+        obj.powersgd.max_grad_norm = max_grad_norm
+        return obj
+
+
+class PowerSGDState(metaclass=_ClipKeyword):
     """Hook state: one codec + residual buffer over ``params`` (the optimizer's order).
 
     ``residual_dtype=torch.float32`` with bfloat16 parameters keeps the error-feedback residual in
@@ -87,7 +100,30 @@ class PowerSGDState:
     stores each parameter's fp32 average straight into its view of its DDP bucket, at rank buckets
     1 to 32. Bit for bit the three stages; ``direct_store_applies()`` tells whether the next
     completion takes it (a compressing step, the library's communicator or the IPC exchange, a plan
-    ``Plan.dst_ok`` reports 1 for). Opt-in: the default is ``False``."""
+    ``Plan.dst_ok`` reports 1 for). Opt-in: the default is ``False``.
+
+    ``max_grad_norm`` (keyword only; also a settable attribute, as on ``PowerSGD``: positive, ``inf``
+    to measure only, or ``None``): what the hook hands back to DDP in the buckets, over all
+    parameters of the iteration, is clipped by its global L2 norm inside the library, on the codec's
+    stream with no host synchronisation: what ``torch.nn.utils.clip_grad_norm_(params, x)`` would do
+    after ``backward()``, ``coef = min(1, x / (norm + 1e-6))``. The caller must NOT clip again. A
+    non-finite norm gives ``coef = NaN`` and leaves everything untouched; the residual is never
+    touched. ``last_grad_norm`` / ``last_clip_coef``: 0-dim float64 device tensors, views of one
+    two-double result buffer that the next completion overwrites; ``None`` until the first clipped
+    completion. What each completion form does with it:
+
+    * three stages: the inner ``PowerSGD`` clips the averages (compressed slab and uncompressed
+      slab; warm-up steps through the same call) before they are gathered into the buckets; with
+      bf16 parameters over an fp32 residual the fp32 averages are clipped before the gather's bf16
+      rounding (``Fp32ResidualPowerSGD``'s rule);
+    * ``fused=True``: every completion runs the three stages while ``max_grad_norm`` is set (the
+      one-call form has rounded to bf16 by the time a norm exists); ``fused_folds()`` reports
+      ``(0, 0)``;
+    * ``direct_store``: the one-call completion is followed by psgd_clip_dst on the same stream: the
+      norm from the low-rank factors and the staged uncompressed sums, the averages scaled where
+      they lie in the buckets, and only when the norm exceeds the threshold. Bit for bit the three
+      stages with the clip. It also needs ``Plan.clip_dst_ok()``; otherwise the completion runs
+      the three stages with the clip."""
 
     fused = False  # (class default: the three-stage completion)
     _direct = False
@@ -138,6 +174,9 @@ class PowerSGDState:
         # after the first iteration; the old tables are dropped)
         self._runs: Dict[int, _BucketRuns] = {}
         self.powersgd = PowerSGD(self.views, config)
+        # norm and coefficient of the latest clipped completion (two doubles; made by the first one
+        # and shared with the inner aggregator, so every completion form writes the same buffer)
+        self._clip_result: Optional[torch.Tensor] = None
         self._seen = [False] * len(self.params)
         self._nseen = 0
         self._pending: List[tuple] = []
@@ -188,6 +227,31 @@ class PowerSGDState:
             self._fail(e, fut)
             raise
         return fut
+
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        return self.powersgd.max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value: Optional[float]) -> None:
+        self.powersgd.max_grad_norm = value
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        return self.powersgd.last_grad_norm
+
+    @property
+    def last_clip_coef(self) -> Optional[torch.Tensor]:
+        return self.powersgd.last_clip_coef
+
+    def _clip_buffer(self) -> torch.Tensor:
+        """The state's result buffer, handed to the inner aggregator as its own."""
+        if self._clip_result is None:
+            inner = self.powersgd
+            self._clip_result = torch.zeros(2, dtype=torch.float64, device=self.residual.device)
+            inner._clip_result = self._clip_result
+            inner.last_grad_norm, inner.last_clip_coef = self._clip_result[0], self._clip_result[1]
+        return self._clip_result
 
     @property
     def direct_store(self) -> bool:
@@ -260,8 +324,11 @@ class PowerSGDState:
     def _fused_applies(self) -> bool:
         """The completion about to run compresses, over the library's communicator or the IPC
         exchange, on a plan psgd_aggregate_mixed_comm_dst / psgd_aggregate_mixed_ipc_dst serves (both
-        step parities: a plan is eligible as a whole)."""
+        step parities: a plan is eligible as a whole). Never while ``max_grad_norm`` is set: the
+        averages are clipped in fp32, before the bf16 rounding."""
         inner = self.powersgd
+        if inner.max_grad_norm is not None:
+            return False
         if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
             return False
         if self._fused_ipc():
@@ -278,7 +345,8 @@ class PowerSGDState:
         """``(fold_in, fold_out)`` of the NEXT completion: ``(0, 1)`` when it takes the one-call form
         (the bf16 rounding of the averages runs inside the codec's final pass; the per-bucket ADD is
         never folded: it runs at bucket arrival, under backward), ``(0, 0)`` when it runs the three
-        stages (``fused=False``, a warm-up step, another transport, a plan the call refuses)."""
+        stages (``fused=False``, a warm-up step, another transport, a plan the call refuses,
+        ``max_grad_norm`` set)."""
         return (0, 1) if self.fused and self._fused_applies() else (0, 0)
 
     def _complete_fused(self) -> None:
@@ -316,7 +384,8 @@ class PowerSGDState:
     def direct_store_applies(self) -> bool:
         """The NEXT completion takes the one-call form of ``direct_store``: it is set, the step
         compresses, the process group runs over the library's communicator or the IPC exchange, and
-        the plan is one psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst serve."""
+        the plan is one psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst serve (with ``max_grad_norm``
+        set: and psgd_clip_dst, ``Plan.clip_dst_ok``)."""
         if not self._direct:
             return False
         inner = self.powersgd
@@ -330,13 +399,17 @@ class PowerSGDState:
                 return False
             world = comm.world
         plan = inner._powersgd._plan
+        if inner.max_grad_norm is not None and plan.clip_dst_ok() != 1:
+            return False
         return plan.dst_ok(0, world) == 1 and plan.dst_ok(1, world) == 1
 
     def _complete_direct(self) -> None:
         """``PowerSGD.aggregate`` of the codec on the residual views as one library call, as
         ``_complete_fused``: the same bookkeeping, the fp32 averages stored by the final pass into the
-        pending buckets' gradient views. No ``_gather``, no output slab."""
+        pending buckets' gradient views. No ``_gather``, no output slab. With ``max_grad_norm``
+        set, psgd_clip_dst follows on the same stream, on the destination tables just filled."""
         inner, codec = self.powersgd, self.powersgd._powersgd
+        stream = _stream(self.residual.device)
         if self._dst_table is None:
             self._dst_table = _psgd_host.PtrTable([list(v.shape) for v in self.views], inner.is_compressed_mask,
                                                   _lib.PSGD_F32, self._dev_index)
@@ -350,10 +423,17 @@ class PowerSGDState:
             # collective, once: exactly as PowerSGD.aggregate sets the exchange up
             codec._ipc_setup(inner._unc.numel if inner._unc is not None else 0)
             codec._plan.aggregate_ipc_dst(inner._table.comp_addr(), self._dst_table.comp_addr(), codec.step_counter,
-                                          _stream(self.residual.device), **kw)
+                                          stream, **kw)
+            world = dist.get_world_size()
         else:
+            comm = self._fused_comm()
             codec._plan.aggregate_comm_dst(inner._table.comp_addr(), self._dst_table.comp_addr(), codec.step_counter,
-                                           self._fused_comm(), _stream(self.residual.device), **kw)
+                                           comm, stream, **kw)
+            world = comm.world
+        if inner.max_grad_norm is not None:
+            ckw = dict(flat=kw["flat"], unc_dst=kw["unc_dst"]) if kw else {}
+            codec._plan.clip_dst(codec.step_counter, world, self._dst_table.comp_addr(), inner.max_grad_norm,
+                                 self._clip_buffer().data_ptr(), stream, **ckw)
         codec.step_counter += 1
         pending, self._pending = self._pending, []
         self._seen = [False] * len(self.params)
@@ -371,7 +451,9 @@ class PowerSGDState:
             if self.direct_store_applies():
                 return self._complete_direct()
             self._dst = [None] * len(self.params)
-        outs = self.powersgd.aggregate(self.views)  # leaves the new residual in self.views
+        if getattr(self.powersgd, "max_grad_norm", None) is not None:
+            self._clip_buffer()
+        outs = self.powersgd.aggregate(self.views)  # leaves the new residual in self.views (clipped: outs)
         pending, self._pending = self._pending, []
         self._seen = [False] * len(self.params)
         self._nseen = 0

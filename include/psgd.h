@@ -31,6 +31,8 @@
  *                          low-rank factors where the plan has them (no reference counterpart)
  *   psgd_clip_dst          the same after a direct-store completion: the averages scaled where
  *                          they lie, inside the DDP buckets
+ *   psgd_guard_outputs     skip a step whose aggregates are not finite, decided and carried out
+ *                          on the device: zero averages and residual, P / Q back to their seed
  *
  * Conventions
  *  - No torch types. Device buffers are plain pointers on the plan's device; `stream` is a
@@ -677,6 +679,45 @@ int psgd_plan_norm_form(const psgd_plan* plan, int64_t step, int32_t world, int3
 int psgd_clip_dst(psgd_plan* plan, int64_t step, int32_t world, void* const* dst, psgd_flat* flat,
                   void* const* unc_dst, double max_norm, double* result, void* stream);
 int psgd_plan_clip_dst_ok(const psgd_plan* plan, int32_t* ok);
+
+/* ------------------------ skipping a non-finite step on the device ----------------------------- */
+/* psgd_guard_outputs: called last after a step (and after its psgd_clip_outputs, never before: the
+ * clip's factor form reads the factors this call may reset) on the same stream. Two launches, no
+ * host synchronisation. k_guard_check scans, for an all-ones exponent field (NaN, +inf, -inf),
+ *   - the plan's bound P state and Q state, psgd_plan_factor_numel elements each (fp32; fp64 on
+ *     PSGD_F64 plans): the gradient enters every product of every iteration, so NaN * x, inf * 0 and
+ *     inf - inf of a non-finite gradient element all land in the out-factor the step leaves there;
+ *     at world size W the factors are all-reduced, so every rank reads the same bits;
+ *   - `flat_out`, the dense uncompressed averages (the plan's dtype), flat_numel elements;
+ * and raises one flag word with an integer atomic max (order-independent). k_guard_apply reads the
+ * word. A finite step: every workgroup returns at once and nothing but result[0] = 0 is written.
+ * Otherwise the step is SKIPPED:
+ *   - every compressed gradient tensor grads[i] (the plan's shapes and dtype; they hold the
+ *     error-feedback residual by now) becomes all-zero bits: exactly its numel elements, a tensor
+ *     needs element alignment only (work items built once per plan split into a head, 16-byte
+ *     vectors and a tail by the item's pointer);
+ *   - `out` (psgd_plan_output_numel elements) and `flat_out` become all-zero bits;
+ *   - P <- p_init and Q <- q_init (psgd_plan_factor_numel elements of the factors' type each), bit
+ *     for bit: with the retained initial draw the codec is a freshly constructed one;
+ *   - result[0] = 1 and result[1] += 1.
+ * The uncompressed INPUTS are not touched: the step itself has zeroed them (psgd_flat_pack).
+ *   `out`       non-NULL: a compressing step; grads, p_init and q_init are required.
+ *               NULL: a warm-up step; only `flat_out` is scanned and zeroed, P and Q are neither read
+ *               nor reset, `grads` is ignored
+ *   `flat_out`  NULL / flat_numel 0: none
+ *   `result`    device, 2 x int64, 8-byte aligned: [0] this call skipped (0 or 1, rewritten by every
+ *               call), [1] the running count (the caller zeroes it once)
+ * Serves every plan: every rank bucket, wide plans, PSGD_F32 / PSGD_BF16 / PSGD_F64; it needs no
+ * recorded term set. The first call makes one device allocation owned by the plan (the flag word,
+ * the work items, the change-detected gradient pointer tables), freed with it; the caller's
+ * workspace layout is untouched. Not covered: finite inputs whose residual arithmetic overflows
+ * while the factors stay finite.
+ * Refusals, all before any launch: a null plan / result, a compressing call with a null grads /
+ * grads[i] / p_init / q_init, flat_numel < 0 or > 0 with a null flat_out: PSGD_ERR_VALUE; a buffer
+ * or gradient not aligned to its element size, `result` not 8-byte aligned: PSGD_ERR_LAYOUT; an
+ * unbound plan: PSGD_ERR_STATE. */
+int psgd_guard_outputs(psgd_plan* plan, void* const* grads, void* out, void* flat_out, int64_t flat_numel,
+                       const void* p_init, const void* q_init, int64_t* result, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,7 +21,11 @@ def optimizer_step(optimizer: torch.optim.Optimizer, aggregator: Aggregator):
     step with the aggregate; afterwards ``p.grad`` holds the error-feedback buffer
     (reference powersgd/__init__.py:7-25). Global-norm clipping of the aggregate goes through the
     aggregator: ``PowerSGD(..., max_grad_norm=x)`` or its ``max_grad_norm`` attribute (the caller
-    has no point between the aggregate and the step at which to clip)."""
+    has no point between the aggregate and the step at which to clip). With
+    ``PowerSGD(..., skip_nonfinite=True)`` a skipped (non-finite) step hands the optimizer zero
+    gradients and leaves ``p.grad`` zero: plain SGD does not move, but the optimizer's own state
+    (momentum, weight decay, step counts) still advances; ``aggregator.last_step_skipped`` is there
+    for callers who want to act on it."""
     params = params_in_optimizer(optimizer)
     grads = [p.grad.data for p in params]  # type: ignore
     avg_grads = aggregator.aggregate(grads)  # subtracts the approximation from grads

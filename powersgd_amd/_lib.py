@@ -96,6 +96,7 @@ _SIGNATURES = {
     "psgd_plan_norm_form": ([_vp, _i64, _i32, _P_i32], _i32),
     "psgd_clip_dst": ([_vp, _i64, _i32, _vp, _vp, _vp, _dbl, _vp, _vp], _i32),
     "psgd_plan_clip_dst_ok": ([_vp, _P_i32], _i32),
+    "psgd_guard_outputs": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -340,6 +341,17 @@ class Plan:
         right after that step on the same stream with the same tables."""
         check(lib().psgd_clip_dst(self._h, step, world, dst, flat._h if flat is not None else None, unc_dst,
                                   float(max_norm), result_ptr, stream))
+
+    # --- skipping a non-finite step on the device
+    def guard_outputs(self, grads, out_ptr: int, flat_ptr: int, flat_numel: int, p_init_ptr: int, q_init_ptr: int,
+                      result_ptr: int, stream: int) -> None:
+        """psgd_guard_outputs: scan the plan's P / Q state and the dense uncompressed slab ``flat_ptr``
+        for a non-finite value and, if there is one, zero ``grads`` (the compressed tensors' pointer
+        table), the compressed slab ``out_ptr`` and the uncompressed slab, and copy ``p_init_ptr`` /
+        ``q_init_ptr`` over P / Q; stream-ordered, after the step and its clip. ``out_ptr = 0``: a
+        warm-up step (the slab only). ``result_ptr``: two device int64 (skipped, running count)."""
+        check(lib().psgd_guard_outputs(self._h, grads, out_ptr or None, flat_ptr or None, flat_numel,
+                                       p_init_ptr or None, q_init_ptr or None, result_ptr or None, stream))
 
     # --- buckets of shape groups (W > 1 comm/compute overlap)
     def set_buckets(self, group_end: Sequence[int]) -> None:

@@ -49,6 +49,7 @@ psgd_plan::~psgd_plan() {
     mixed_release(this);
     direct_release(this);
     norm_release(this);
+    guard_release(this);
     if (xerr_host) (void)hipHostFree(xerr_host);
     if (stamp_buf) (void)hipFree(stamp_buf);
 }

@@ -6,6 +6,7 @@
 //   psgd_mixed.cpp     psgd_aggregate_mixed[_comm]: admission of the mixed instances, fold queries
 //   psgd_direct.cpp    psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst: admission, state, entry points
 //   psgd_norm.cpp      psgd_clip_outputs / psgd_plan_norm_form: form choice, state, launches
+//   psgd_guard.cpp     psgd_guard_outputs: skipping a non-finite step (state, launches)
 //   psgd_ipc.cpp       the IPC exchange arena and psgd_aggregate_ipc
 //   psgd_flat.cpp      flat pack and DDP run tables
 //   psgd_comm.cpp      the communicator behind psgd_aggregate_comm
@@ -440,6 +441,10 @@ struct psgd_plan {
     int norm_env = 0;  // PSGD_NORM_FORM, read at create: 0 auto, 1 factors, 2 stream (A/B runs)
     struct Norm;
     Norm* norm = nullptr;
+    // psgd_guard_outputs (psgd_guard.cpp): device state of its own like Norm (the flag word, the
+    // gradient tensors' work items, the gradient pointer tables), made by the first call
+    struct Guard;
+    Guard* guard = nullptr;
     int64_t xslot_off(int64_t step, int it) const {  // byte offset of a slot in every buffer
         return kXchgHeader + ((step & 1) * iters + it) * ipc_slot * int64_t(sizeof(float));
     }
@@ -676,6 +681,8 @@ bool direct_shape_ok(const psgd_plan* p);
 int direct_select(psgd_plan* p, void* const* dst, const psgd_flat* f, void* const* unc_dst, hipStream_t s, DirectDst* t);
 // psgd_norm.cpp: frees the plan's norm state
 void norm_release(psgd_plan* p);
+// psgd_guard.cpp: frees the plan's guard state
+void guard_release(psgd_plan* p);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
 int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
 // psgd_step.cpp: the world-size-W step of psgd_aggregate_comm; with `mix`, of psgd_aggregate_mixed_comm;

@@ -62,15 +62,16 @@ class _BucketRuns:
 
 
 class _ClipKeyword(type):
-    """``PowerSGDState(config, params, ..., fused=False, max_grad_norm=None)``: the keyword is taken at
-    the class call, checked before any device work, and handed to the inner aggregator once it
-    exists (as ``Fp32ResidualPowerSGD`` takes it). ``__init__`` keeps the parameter list ``(config,
+    """``PowerSGDState(config, params, ..., fused=False, max_grad_norm=None, skip_nonfinite=False)``: the
+    keywords are taken at the class call, ``max_grad_norm`` checked before any device work, and
+    handed to the inner aggregator once it exists (as ``Fp32ResidualPowerSGD`` takes them). ``__init__`` keeps the parameter list ``(config,
     params, process_group, residual_dtype, fused)`` that existing callers and tests inspect."""
 
-    def __call__(cls, *args, max_grad_norm: Optional[float] = None, **kwargs):
+    def __call__(cls, *args, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, **kwargs):
         max_grad_norm = _check_max_grad_norm(max_grad_norm)
         obj = super().__call__(*args, **kwargs)
         obj.powersgd.max_grad_norm = max_grad_norm
+        obj.powersgd.skip_nonfinite = skip_nonfinite  # (``PowerSGD.skip_nonfinite``, taken the same way)
         return obj
 
 
@@ -123,7 +124,16 @@ class PowerSGDState(metaclass=_ClipKeyword):
       norm from the low-rank factors and the staged uncompressed sums, the averages scaled where
       they lie in the buckets, and only when the norm exceeds the threshold. Bit for bit the three
       stages with the clip. It also needs ``Plan.clip_dst_ok()``; otherwise the completion runs
-      the three stages with the clip."""
+      the three stages with the clip.
+
+    ``skip_nonfinite`` (keyword only; ``PowerSGD.skip_nonfinite`` of the inner aggregator, settable
+    until the first backward): an iteration whose aggregates are not finite is skipped on the
+    device, with no host synchronisation: the buckets come back all zero, ``residual`` is zeroed and
+    P / Q go back to their seed; ``last_step_skipped`` / ``skipped_steps`` are the inner
+    aggregator's. While it is set every completion runs the three stages (the inner aggregator
+    zeroes the averages and the residual views before they are gathered into the buckets):
+    ``fused_folds()`` reports ``(0, 0)`` and ``direct_store_applies()`` ``False``, since the one-call
+    forms have already stored into the buckets by the time a verdict exists."""
 
     fused = False  # (class default: the three-stage completion)
     _direct = False
@@ -237,6 +247,24 @@ class PowerSGDState(metaclass=_ClipKeyword):
         self.powersgd.max_grad_norm = value
 
     @property
+    def skip_nonfinite(self) -> bool:
+        return self.powersgd.skip_nonfinite
+
+    @skip_nonfinite.setter
+    def skip_nonfinite(self, on: bool) -> None:
+        if bool(on) != self.powersgd.skip_nonfinite and self._pending:
+            raise ValueError("skip_nonfinite is set before the first backward")
+        self.powersgd.skip_nonfinite = on
+
+    @property
+    def last_step_skipped(self) -> Optional[torch.Tensor]:
+        return self.powersgd.last_step_skipped
+
+    @property
+    def skipped_steps(self) -> Optional[torch.Tensor]:
+        return self.powersgd.skipped_steps
+
+    @property
     def last_grad_norm(self) -> Optional[torch.Tensor]:
         return self.powersgd.last_grad_norm
 
@@ -325,9 +353,9 @@ class PowerSGDState(metaclass=_ClipKeyword):
         """The completion about to run compresses, over the library's communicator or the IPC
         exchange, on a plan psgd_aggregate_mixed_comm_dst / psgd_aggregate_mixed_ipc_dst serves (both
         step parities: a plan is eligible as a whole). Never while ``max_grad_norm`` is set: the
-        averages are clipped in fp32, before the bf16 rounding."""
+        averages are clipped in fp32, before the bf16 rounding; never while ``skip_nonfinite`` is set."""
         inner = self.powersgd
-        if inner.max_grad_norm is not None:
+        if inner.max_grad_norm is not None or inner.skip_nonfinite:
             return False
         if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
             return False
@@ -346,7 +374,7 @@ class PowerSGDState(metaclass=_ClipKeyword):
         (the bf16 rounding of the averages runs inside the codec's final pass; the per-bucket ADD is
         never folded: it runs at bucket arrival, under backward), ``(0, 0)`` when it runs the three
         stages (``fused=False``, a warm-up step, another transport, a plan the call refuses,
-        ``max_grad_norm`` set)."""
+        ``max_grad_norm`` or ``skip_nonfinite`` set)."""
         return (0, 1) if self.fused and self._fused_applies() else (0, 0)
 
     def _complete_fused(self) -> None:
@@ -385,10 +413,12 @@ class PowerSGDState(metaclass=_ClipKeyword):
         """The NEXT completion takes the one-call form of ``direct_store``: it is set, the step
         compresses, the process group runs over the library's communicator or the IPC exchange, and
         the plan is one psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst serve (with ``max_grad_norm``
-        set: and psgd_clip_dst, ``Plan.clip_dst_ok``)."""
+        set: and psgd_clip_dst, ``Plan.clip_dst_ok``). Never while ``skip_nonfinite`` is set."""
         if not self._direct:
             return False
         inner = self.powersgd
+        if inner.skip_nonfinite:  # the verdict comes after the step: the three stages
+            return False
         if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
             return False
         if self._fused_ipc():

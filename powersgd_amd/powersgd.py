@@ -172,15 +172,38 @@ class PowerSGD(Aggregator):
     whose norm is below the threshold never re-reads its outputs. ``last_grad_norm`` and
     ``last_clip_coef`` are 0-dim float64 device tensors, views of one result buffer that the next
     call overwrites. The gradients still become the residual; clipping never touches it. ``None``
-    (default): every code path is the unclipped one."""
+    (default): every code path is the unclipped one.
 
-    def __init__(self, params: List[torch.Tensor], config: Config, *, max_grad_norm: Optional[float] = None):
+    ``skip_nonfinite`` (keyword; a property that can be set until the first ``aggregate``; not in
+    the reference): a guard at the end of every ``aggregate``, on the codec's stream with no host
+    synchronisation (psgd_guard_outputs). It scans what the step has already produced and that is
+    small, the P / Q state and the dense slab of uncompressed averages, for NaN / inf: a non-finite
+    gradient element enters every product of the step, so it is in the out-factor left there, and
+    at world size W these are all-reduced, so every rank takes the same decision. A finite step is
+    not touched. Otherwise the step is *skipped*: every returned average and every gradient handed
+    in (the error-feedback memory) becomes all-zero bits, P and Q go back to ``reset_p`` /
+    ``reset_q`` (clones of the constructor's seed-0 draw, made when the guard is enabled; device
+    tensors that may be overwritten), and both step counters advance as usual: the codec is a
+    freshly constructed one, except for its counters. ``last_step_skipped`` (0 or 1, rewritten by
+    every guarded call) and ``skipped_steps`` (cumulative) are 0-dim int64 device tensors, views of
+    one two-element buffer; ``None`` while the guard is off. With ``max_grad_norm`` the guard runs
+    after the clip; on a skipped step ``last_clip_coef`` stays NaN. Not covered: finite inputs
+    whose residual arithmetic overflows while the factors stay finite."""
+
+    def __init__(self, params: List[torch.Tensor], config: Config, *, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         self.config = config
         self._max_grad_norm: Optional[float] = None
         self.max_grad_norm = max_grad_norm
         self._clip_result: Optional[torch.Tensor] = None
         self.last_grad_norm: Optional[torch.Tensor] = None
         self.last_clip_coef: Optional[torch.Tensor] = None
+        self._skip_nonfinite = False
+        self._guard_result: Optional[torch.Tensor] = None
+        self.last_step_skipped: Optional[torch.Tensor] = None
+        self.skipped_steps: Optional[torch.Tensor] = None
+        self.reset_p: Optional[torch.Tensor] = None
+        self.reset_q: Optional[torch.Tensor] = None
         self.device = list(params)[0].device
         self.is_compressed_mask = [self._should_compress(p.shape) for p in params]
         self.step_counter = 0
@@ -205,6 +228,7 @@ class PowerSGD(Aggregator):
         for c in self.is_compressed_mask:
             self._order.append(ic if c else iu)
             ic, iu = (ic + 1, iu) if c else (ic, iu + 1)
+        self.skip_nonfinite = skip_nonfinite
 
     @property
     def max_grad_norm(self) -> Optional[float]:
@@ -213,6 +237,32 @@ class PowerSGD(Aggregator):
     @max_grad_norm.setter
     def max_grad_norm(self, value: Optional[float]) -> None:
         self._max_grad_norm = _check_max_grad_norm(value)
+
+    @property
+    def skip_nonfinite(self) -> bool:
+        return self._skip_nonfinite
+
+    @skip_nonfinite.setter
+    def skip_nonfinite(self, on: bool) -> None:
+        on = bool(on)
+        if on == self._skip_nonfinite:
+            return
+        if self.step_counter > 0:
+            raise ValueError("skip_nonfinite is set before the first aggregate")
+        self._skip_nonfinite = on
+        if on and self._guard_result is None:
+            codec = self._powersgd
+            # the seed-0 draw a skipped step goes back to (no step has run: the state still holds it)
+            self.reset_p, self.reset_q = codec._ps_buffer.clone(), codec._qs_buffer.clone()
+            self._guard_result = torch.zeros(2, dtype=torch.int64, device=self.device)
+            self.last_step_skipped, self.skipped_steps = self._guard_result[0], self._guard_result[1]
+
+    def _guard(self, comp_addr: int, out_ptr: int, flat_ptr: int, flat_numel: int) -> None:
+        """The guard on the averages the step (and its clip) just enqueued, on the codec's stream:
+        ``comp_addr`` the pointer table of the compressed gradients handed in (0 with ``out_ptr`` 0:
+        a warm-up step)."""
+        self._powersgd._plan.guard_outputs(comp_addr or None, out_ptr, flat_ptr, flat_numel, self.reset_p.data_ptr(),
+                                           self.reset_q.data_ptr(), self._guard_result.data_ptr(), _stream(self.device))
 
     def _clip(self, out_ptr: int, flat_ptr: int, flat_numel: int) -> None:
         """Clip the averages the step just enqueued (compressed slab, dense uncompressed slab) on
@@ -233,12 +283,16 @@ class PowerSGD(Aggregator):
         self.step_counter += 1
         if self.step_counter <= self.config.start_compressing_after_num_steps:
             outs = self._allreduce.aggregate(gradients)
-            if self._max_grad_norm is not None and len(outs) > 0:
+            if (self._max_grad_norm is not None or self._skip_nonfinite) and len(outs) > 0:
                 entry = self._allreduce._last
                 if entry.dtype != self._powersgd.dtype:
-                    raise RuntimeError(f"max_grad_norm: gradients are {entry.dtype}, the codec's are "
+                    what = "max_grad_norm" if self._max_grad_norm is not None else "skip_nonfinite"
+                    raise RuntimeError(f"{what}: gradients are {entry.dtype}, the codec's are "
                                        f"{self._powersgd.dtype}")
-                self._clip(0, entry.slab.data_ptr(), entry.numel)
+                if self._max_grad_norm is not None:
+                    self._clip(0, entry.slab.data_ptr(), entry.numel)
+                if self._skip_nonfinite:
+                    self._guard(0, 0, entry.slab.data_ptr(), entry.numel)
             return outs
         if not isinstance(gradients, list):
             gradients = list(gradients)
@@ -277,6 +331,10 @@ class PowerSGD(Aggregator):
             u = self._unc
             self._clip(codec._slab.data_ptr(), u.slab.data_ptr() if u is not None else 0,
                        u.numel if u is not None else 0)
+        if self._skip_nonfinite:  # last on every path, after the clip (whose factor form reads P / Q)
+            u = self._unc
+            self._guard(self._table.comp_addr(), codec._slab.data_ptr(), u.slab.data_ptr() if u is not None else 0,
+                        u.numel if u is not None else 0)
         return [outs[i] for i in self._order]  # reference _merge :86-99
 
     def close(self) -> None:

@@ -44,15 +44,16 @@ from .utils import is_distributed
 
 
 class _ClipKeyword(ABCMeta):
-    """``Fp32ResidualPowerSGD(params, config, fused=False, max_grad_norm=None)``: the keyword is taken
-    at the class call, checked before any device work, and handed to the inner fp32 aggregator once
-    it exists. ``__init__`` keeps the parameter list ``(params, config, fused)`` that existing callers
+    """``Fp32ResidualPowerSGD(params, config, fused=False, max_grad_norm=None, skip_nonfinite=False)``:
+    the keywords are taken at the class call, ``max_grad_norm`` checked before any device work, and
+    handed to the inner fp32 aggregator once it exists. ``__init__`` keeps the parameter list ``(params, config, fused)`` that existing callers
     and tests inspect."""
 
-    def __call__(cls, *args, max_grad_norm: Optional[float] = None, **kwargs):
+    def __call__(cls, *args, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, **kwargs):
         max_grad_norm = _check_max_grad_norm(max_grad_norm)
         obj = super().__call__(*args, **kwargs)
         obj.inner.max_grad_norm = max_grad_norm
+        obj.inner.skip_nonfinite = skip_nonfinite  # (``PowerSGD.skip_nonfinite``, taken the same way)
         return obj
 
 
@@ -62,7 +63,11 @@ class Fp32ResidualPowerSGD(Aggregator, metaclass=_ClipKeyword):
     (the fp32 ``PowerSGD`` over ``views``). ``fused``: take the one-call fused step where it
     applies (module docstring); same results, bit for bit. ``max_grad_norm`` (keyword, also a
     settable attribute): global-norm clipping by the inner aggregator (``PowerSGD.max_grad_norm``):
-    the fp32 averages are clipped before the GATHER rounds them to bf16."""
+    the fp32 averages are clipped before the GATHER rounds them to bf16. ``skip_nonfinite`` (keyword):
+    ``PowerSGD.skip_nonfinite`` of the inner aggregator: a skipped step zeroes the fp32 averages and
+    ``residual`` before the GATHER, so the bf16 averages are zero too. While it is set every step runs
+    the three stages, as under ``max_grad_norm``: the one-call forms have already rounded and stored
+    by the time a verdict exists."""
 
     def __init__(self, params: List[torch.Tensor], config: Config, fused: bool = False):
         params = list(params)
@@ -118,6 +123,24 @@ class Fp32ResidualPowerSGD(Aggregator, metaclass=_ClipKeyword):
         self.inner.max_grad_norm = value
 
     @property
+    def skip_nonfinite(self) -> bool:
+        """``PowerSGD.skip_nonfinite`` of ``inner`` (settable until the first ``aggregate``). While
+        set, the step runs the three stages even under ``fused=True``."""
+        return self.inner.skip_nonfinite
+
+    @skip_nonfinite.setter
+    def skip_nonfinite(self, on: bool) -> None:
+        self.inner.skip_nonfinite = on
+
+    @property
+    def last_step_skipped(self):
+        return self.inner.last_step_skipped
+
+    @property
+    def skipped_steps(self):
+        return self.inner.skipped_steps
+
+    @property
     def last_grad_norm(self):
         return self.inner.last_grad_norm
 
@@ -166,6 +189,8 @@ class Fp32ResidualPowerSGD(Aggregator, metaclass=_ClipKeyword):
         inner = self.inner
         if inner.max_grad_norm is not None:  # clipped before the bf16 rounding: the three stages
             return False
+        if inner.skip_nonfinite:  # the verdict comes after the step: zeroed before the GATHER
+            return False
         if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
             return False
         plan = inner._powersgd._plan
@@ -182,7 +207,8 @@ class Fp32ResidualPowerSGD(Aggregator, metaclass=_ClipKeyword):
         pass (psgd_plan_mixed_folds; over a communicator or the IPC exchange
         psgd_plan_mixed_folds_comm: ``(0, 1)``);
         ``(0, 0)`` whenever that call runs the three-stage flow (``fused=False``, a warm-up step, a
-        process group on another transport, a plan the fused call refuses)."""
+        process group on another transport, a plan the fused call refuses, ``max_grad_norm`` or
+        ``skip_nonfinite`` set)."""
         if not (self.fused and self._fused_applies()):
             return (0, 0)
         codec = self.inner._powersgd

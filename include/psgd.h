@@ -487,6 +487,39 @@ int psgd_aggregate_mixed_comm(psgd_plan* plan, void* const* grads_bf16, void* co
 int psgd_plan_mixed_folds_comm(const psgd_plan* plan, int64_t step, int32_t world,
                                int32_t* fold_in, int32_t* fold_out);
 
+/* ------------------- ... on a wide plan (effective ranks 33-128) ------------------------------- */
+/* psgd_aggregate_mixed_flat and psgd_aggregate_mixed_comm refuse wide plans; these two entries
+ * serve them, with the same arguments and the same definitions (bit for bit, nothing else
+ * observable): the ADD on the compressed and the uncompressed tensors, psgd_aggregate_flat (or
+ * psgd_aggregate_comm) on the residual, the bf16 round-to-nearest-even of both outputs.
+ * Where the stages run:
+ *   ingest       the run-table ADD, a launch of the library's, first
+ *   iterations   the wide products, reductions and orthonormalisation (and psgd_aggregate_comm's
+ *                collectives, in its order and count), untouched
+ *   output fold  every step: the final pass is k_wide_apply_mix (psgd_wide_mixed.hip):
+ *                k_wide_apply<float>'s tile and MFMA sequence with the factor blocks staged in LDS
+ *                once per workgroup, the fp32 residual stored in place and the averages as bf16.
+ *                No fp32 output slab exists.
+ *   flat tail    staged in the plan's fp32 buffer in both forms: stage = (x + float(g)) / W,
+ *                x = g = +0.0 in a launch of its own before the first collective, flat_out_bf16 =
+ *                bf16(stage) in a launch of its own after the final pass.
+ * Eligible: a bound PSGD_F32 wide plan of one bucket whose two forms of k_wide_apply_mix (shared
+ * terms; two term sets) are both admitted (at least two waves per SIMD, no scratch; asked of the
+ * runtime). Refusals: the codes and the order of the checks of psgd_aggregate_mixed_flat /
+ * psgd_aggregate_mixed_comm, before anything is launched or any collective issued; the
+ * communicator stays usable; poisoning as there.
+ * psgd_plan_mixed_wide_ok: *ok = 1 for an eligible plan (`world` >= 1 is checked and otherwise
+ * unused: a plan is eligible for every world size or none), else 0. On an unbound plan the answer
+ * is this build's on the current device. */
+int psgd_aggregate_mixed_wide(psgd_plan* plan, void* const* grads_bf16, void* const* residual,
+                              void* out_bf16, int64_t step, psgd_flat* flat, void* const* unc_bf16,
+                              void* const* unc_residual, void* flat_out_bf16, void* stream);
+int psgd_aggregate_mixed_wide_comm(psgd_plan* plan, void* const* grads_bf16, void* const* residual,
+                                   void* out_bf16, int64_t step, psgd_flat* flat,
+                                   void* const* unc_bf16, void* const* unc_residual,
+                                   void* flat_out_bf16, psgd_comm* comm, void* stream);
+int psgd_plan_mixed_wide_ok(const psgd_plan* plan, int32_t world, int32_t* ok);
+
 /* ------------------- ... with the averages stored at per-tensor destinations (DDP hook) -------- */
 /* The completion of the DDP communication hook with an fp32 residual of bf16 gradients. The hook
  * adds every bucket into the residual when it arrives, so `residual` already holds residual +

@@ -85,6 +85,9 @@ _SIGNATURES = {
     "psgd_plan_mixed_folds": ([_vp, _i64, _P_i32, _P_i32], _i32),
     "psgd_aggregate_mixed_comm": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_plan_mixed_folds_comm": ([_vp, _i64, _i32, _P_i32, _P_i32], _i32),
+    "psgd_aggregate_mixed_wide": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_aggregate_mixed_wide_comm": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_mixed_wide_ok": ([_vp, _i32, _P_i32], _i32),
     "psgd_aggregate_mixed_comm_dst": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_plan_mixed_folds_dst": ([_vp, _i64, _i32, _P_i32], _i32),
     "psgd_aggregate_mixed_ipc": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
@@ -268,6 +271,26 @@ class Plan:
         check(lib().psgd_aggregate_mixed_comm(self._h, grads_bf16, residual, out_ptr, step,
                                               flat._h if flat is not None else None, unc_bf16, unc_residual,
                                               flat_out or None, comm._h if comm is not None else None, stream))
+
+    # --- ... on a wide plan (effective ranks 33-128)
+    def mixed_wide_ok(self, world: int = 1) -> int:
+        """1 where ``aggregate_mixed_wide`` / ``aggregate_mixed_wide_comm`` serve this plan
+        (psgd_plan_mixed_wide_ok), 0 for a plan they refuse."""
+        ok = _i32()
+        check(lib().psgd_plan_mixed_wide_ok(self._h, world, ctypes.byref(ok)))
+        return int(ok.value)
+
+    def aggregate_mixed_wide(self, grads_bf16, residual, out_ptr: int, step: int, stream: int, comm: "Comm" = None,
+                             flat=None, unc_bf16=None, unc_residual=None, flat_out: int = 0) -> None:
+        """psgd_aggregate_mixed_wide (``comm`` given: psgd_aggregate_mixed_wide_comm). Raises
+        ``ValueError`` for a plan it does not serve, before anything is launched or any collective
+        issued."""
+        args = (self._h, grads_bf16, residual, out_ptr, step, flat._h if flat is not None else None, unc_bf16,
+                unc_residual, flat_out or None)
+        if comm is None:
+            check(lib().psgd_aggregate_mixed_wide(*args, stream))
+        else:
+            check(lib().psgd_aggregate_mixed_wide_comm(*args, comm._h, stream))
 
     # --- ... with the bf16 averages stored at per-tensor destinations (the DDP hook's completion)
     def mixed_folds_dst(self, step: int, world: int) -> int:

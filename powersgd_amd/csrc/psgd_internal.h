@@ -382,6 +382,11 @@ struct WideArgs {
 hipError_t launch_wide_product(int dtype, int R, bool even, const WideArgs& a, int ntiles, hipStream_t s);
 hipError_t launch_wide_reduce(const WideArgs& a, int nitems, hipStream_t s);
 hipError_t launch_wide_apply(int dtype, int R, const WideArgs& a, int ntiles, hipStream_t s);
+// psgd_wide_mixed.hip (psgd_aggregate_mixed_wide[_comm]): k_wide_apply<float>'s pass with the factor
+// blocks staged in LDS and the output stored as bf16 (`a.out` a bf16 buffer; a.shared picks the
+// form). ntiles == 0: no launch; `*waves` (if non-null) receives the resident waves per SIMD of
+// the instance that would run, 0 when it uses scratch.
+hipError_t launch_wide_apply_mix(int R, const WideArgs& a, int ntiles, hipStream_t s, int* waves);
 // Orthonormalisation of a wide plan's units in three launches (psgd_wide.hip): the panels' Gram
 // matrices over row blocks of kWideGramRows rows, one workgroup per unit for the r x r chain
 // (rank-1 units: the joint group norm; rejected panels: Householder QR), then Y = X M' over the

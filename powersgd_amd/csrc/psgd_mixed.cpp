@@ -21,6 +21,10 @@
 // The residual already holds residual + gradients (the hook adds each bucket on arrival), so the
 // call is psgd_aggregate_comm on the residual and the GATHER alone, and the final pass stores each
 // tensor's bf16 average at the tensor's own destination (MixDst): no ADD, no dense output.
+// psgd_aggregate_mixed_wide / psgd_aggregate_mixed_wide_comm / psgd_plan_mixed_wide_ok: the first two
+// forms on a wide plan (effective ranks 33-128), which every entry above refuses. The ADD, then
+// psgd_aggregate_flat / psgd_aggregate_comm on the residual with k_wide_apply_mix (psgd_wide_mixed.hip)
+// as the final pass, the flat tail staged in fp32 in both forms (aggregate_wide_mix_ctx).
 // psgd_aggregate_mixed_ipc / psgd_aggregate_mixed_ipc_dst: the same two forms over the plan's IPC
 // exchange session (psgd_aggregate_ipc on the residual between the ADD and the GATHER). Admission is
 // the communicator forms' (the output pass takes the same route); the flat tail needs no staging:
@@ -41,6 +45,16 @@ const char* ineligible(const psgd_plan* p) {
     if (p->wide() || !(rb == 1 || rb == 2 || rb == 4 || rb == 16 || rb == 32))
         return "psgd_aggregate_mixed serves rank buckets 1, 2, 4, 16 and 32 (not 8, not ranks above 32)";
     if (p->spans.size() > 1) return "psgd_aggregate_mixed takes a plan of one bucket";
+    return nullptr;
+}
+
+// psgd_aggregate_mixed_wide[_comm]: what the entries above refuse by rank, effective ranks 33-128
+const char* ineligible_wide(const psgd_plan* p) {
+    if (p->dtype != PSGD_F32)
+        return "psgd_aggregate_mixed_wide takes an fp32 plan (the fp32 residual of bf16 gradients)";
+    if (!p->wide())
+        return "psgd_aggregate_mixed_wide serves ranks 33-128 (psgd_aggregate_mixed: rank buckets 1, 2, 4, 16 and 32)";
+    if (p->spans.size() > 1) return "psgd_aggregate_mixed_wide takes a plan of one bucket";
     return nullptr;
 }
 
@@ -121,6 +135,22 @@ void admit_dst(psgd_plan* p) {
             m.dst_out[one][par] = admitted(p, p->out_route(par, one ? 1 : 2, comm_out_ctx(&none, &tabs)), none, &tabs);
 }
 
+// psgd_aggregate_mixed_wide[_comm]: both forms of k_wide_apply_mix<rbucket> (a communicator's world
+// size is known only at the call, and a plan is eligible or not as a whole)
+void admit_wide(psgd_plan* p) {
+    psgd_plan::Mixed& m = *p->mixed;
+    if (m.wide_asked) return;
+    m.wide_asked = true;
+    for (int sh = 0; sh < 2; ++sh) {
+        WideArgs a{};
+        a.shared = sh;
+        int w = 0;
+        m.wide_ok[sh] = admitted(launch_wide_apply_mix(p->rbucket, a, 0, nullptr, &w), w);
+    }
+}
+
+bool wide_eligible(const psgd_plan* p) { return p->mixed->wide_ok[0] && p->mixed->wide_ok[1]; }
+
 bool dst_eligible(const psgd_plan* p, int world) {
     const psgd_plan::Mixed& m = *p->mixed;
     const int one = world == 1 ? 1 : 0;
@@ -190,15 +220,18 @@ int unc_table(psgd_plan::Mixed& m, psgd_flat* f, void* const* unc, void* const* 
     return PSGD_OK;
 }
 
-// the plan's eligibility, then every tensor's two pointers
-int check_tensors(const psgd_plan* p, void* const* grads, void* const* residual) {
-    if (const char* why = ineligible(p)) return fail(PSGD_ERR_VALUE, why);
+// the plan's eligibility (`why`: the refusal, or null), then every tensor's two pointers
+int check_tensors(const psgd_plan* p, const char* why, void* const* grads, void* const* residual) {
+    if (why) return fail(PSGD_ERR_VALUE, why);
     for (size_t i = 0; i < p->shapes.size(); ++i) {
         if (!grads[i] || !residual[i]) return fail(PSGD_ERR_VALUE, "null gradient pointer");
         if (reinterpret_cast<uintptr_t>(grads[i]) % 2) return fail(PSGD_ERR_LAYOUT, "bf16 gradients must be 2-byte aligned");
         if (reinterpret_cast<uintptr_t>(residual[i]) % 4) return fail(PSGD_ERR_LAYOUT, "the fp32 residual must be 4-byte aligned");
     }
     return PSGD_OK;
+}
+int check_tensors(const psgd_plan* p, void* const* grads, void* const* residual) {
+    return check_tensors(p, ineligible(p), grads, residual);
 }
 
 // A fold query: admission is a property of this build's kernels on the device (asked once per
@@ -291,6 +324,33 @@ int mixed_comm_impl(psgd_plan* p, void* const* grads, void* const* residual, voi
     }
     if (int st = psgd_runs_add_list(m.add, grads, residual, 1, s)) return st;
     return aggregate_comm_ctx(p, residual, out, step, f, unc_residual, flat_out, comm, s, &x);
+}
+
+// psgd_aggregate_mixed_wide (`comm` null) / psgd_aggregate_mixed_wide_comm past their argument
+// checks (`refused` as in mixed_comm_impl). The wide kernels test each tensor's alignment
+// themselves, so admission needs no pointers and comes first; the ADD is the first launch
+int mixed_wide_impl(psgd_plan* p, void* const* grads, void* const* residual, void* out, int64_t step, psgd_flat* f,
+                    void* const* unc, void* const* unc_residual, void* flat_out, psgd_comm* comm, hipStream_t s,
+                    bool* refused) {
+    DevScope scope(p->device);
+    if (int st = ensure(p)) return st;
+    psgd_plan::Mixed& m = *p->mixed;
+    admit_wide(p);
+    if (!wide_eligible(p)) {
+        *refused = true;
+        return fail(PSGD_ERR_VALUE, "psgd_aggregate_mixed_wide: k_wide_apply_mix is not admitted for this plan's rank "
+                                    "bucket (two waves per SIMD, no scratch)");
+    }
+    MixArgs x{};
+    if (f) {
+        if (int st = unc_table(m, f, unc, unc_residual, s)) return st;
+        if (int st = stage_room(m, f, s)) return st;
+        PSGD_HIP(m.unc_tab.select(unc, s));
+        x.unc_src = m.unc_tab.table();
+        x.stage = m.stage;
+    }
+    if (int st = psgd_runs_add_list(m.add, grads, residual, 1, s)) return st;
+    return aggregate_wide_mix_ctx(p, residual, out, step, f, unc_residual, flat_out, comm, s, x);
 }
 
 // psgd_aggregate_mixed_comm_dst past its argument checks (`refused` as in mixed_comm_impl)
@@ -452,6 +512,57 @@ int psgd_aggregate_mixed_comm(psgd_plan* p, void* const* grads_bf16, void* const
                                    unc_residual, flat_out_bf16, comm, static_cast<hipStream_t>(stream), &refused);
     // a failure past the argument checks can leave this rank's collective sequence short of its
     // peers': the communicator refuses every later call (psgd_comm.cpp, comm_poison)
+    if (st && !refused) comm_poison(comm, psgd_last_error());
+    return st;
+}
+
+int psgd_plan_mixed_wide_ok(const psgd_plan* plan, int32_t world, int32_t* ok) {
+    if (!plan || !ok) return fail(PSGD_ERR_VALUE, "null argument");
+    if (world < 1) return fail(PSGD_ERR_VALUE, "world size must be >= 1");
+    *ok = 0;
+    if (ineligible_wide(plan)) return PSGD_OK;
+    return query_folds(plan, admit_wide, [&](const psgd_plan* p) { *ok = wide_eligible(p) ? 1 : 0; });
+}
+
+int psgd_aggregate_mixed_wide(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,
+                              psgd_flat* f, void* const* unc_bf16, void* const* unc_residual, void* flat_out_bf16,
+                              void* stream) {
+    if (int st = check_call(p && grads_bf16 && residual && out_bf16, p && p->bound, step >= 0, "step out of range"))
+        return st;
+    if (int st = check_out(out_bf16)) return st;
+    const bool has_flat = f && f->total > 0;
+    if (has_flat)
+        if (int st = check_flat(f, unc_bf16 && unc_residual && flat_out_bf16, f->dtype == PSGD_F32 && f->device == p->device,
+                                PSGD_ERR_VALUE, "psgd_aggregate_mixed_wide takes an fp32 flat plan (the uncompressed tensors' "
+                                                "residual) on the codec's device"))
+            return st;
+    if (int st = check_tensors(p, ineligible_wide(p), grads_bf16, residual)) return st;
+    bool refused = false;
+    return mixed_wide_impl(p, grads_bf16, residual, out_bf16, step, has_flat ? f : nullptr, unc_bf16, unc_residual,
+                           flat_out_bf16, nullptr, static_cast<hipStream_t>(stream), &refused);
+}
+
+int psgd_aggregate_mixed_wide_comm(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16,
+                                   int64_t step, psgd_flat* f, void* const* unc_bf16, void* const* unc_residual,
+                                   void* flat_out_bf16, psgd_comm* comm, void* stream) {
+    if (int st = check_call(p && grads_bf16 && residual && out_bf16 && comm, p && p->bound, step >= 0, "step out of range"))
+        return st;
+    if (int st = check_out(out_bf16)) return st;
+    const bool has_flat = f && f->total > 0;
+    if (has_flat)
+        if (int st = check_flat(f, unc_bf16 && unc_residual && flat_out_bf16, f->dtype == PSGD_F32 && f->device == p->device,
+                                PSGD_ERR_VALUE, "psgd_aggregate_mixed_wide_comm takes an fp32 flat plan (the uncompressed "
+                                                "tensors' residual) on the codec's device"))
+            return st;
+    if (int st = check_tensors(p, ineligible_wide(p), grads_bf16, residual)) return st;
+    // a poisoned communicator is refused before the step launches anything
+    std::string why;
+    if (comm_poisoned(comm, &why))
+        return fail(PSGD_ERR_STATE, ("communicator unusable after an earlier failure: " + why).c_str());
+    bool refused = false;
+    const int st = mixed_wide_impl(p, grads_bf16, residual, out_bf16, step, has_flat ? f : nullptr, unc_bf16, unc_residual,
+                                   flat_out_bf16, comm, static_cast<hipStream_t>(stream), &refused);
+    // a failure past the argument checks can leave this rank's collective sequence short of its peers'
     if (st && !refused) comm_poison(comm, psgd_last_error());
     return st;
 }

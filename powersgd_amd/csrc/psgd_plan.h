@@ -396,6 +396,10 @@ struct psgd_plan {
         uint64_t dst_key = ~uint64_t(0);
         bool dst_out[2][2] = {};
         TableCache dst, unc_dst;
+        // psgd_aggregate_mixed_wide[_comm] (wide plans): admission of k_wide_apply_mix<rbucket>
+        // ([0]: two term sets, [1]: shared), asked once (its tiles never change)
+        bool wide_asked = false;
+        bool wide_ok[2] = {};
     };
     Mixed* mixed = nullptr;
     // psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst (psgd_direct.cpp): state of its own like
@@ -691,6 +695,14 @@ int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s,
 int aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
                        void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix, const MixDst* dst = nullptr,
                        const DirectDst* fdst = nullptr);
+
+// psgd_step.cpp: the step of psgd_aggregate_mixed_wide (`comm` null: world size 1) and
+// psgd_aggregate_mixed_wide_comm on a wide fp32 plan, after the ADD: `grads` the fp32 residual,
+// `out` / `flat_out` bf16, `unc` the uncompressed tensors' fp32 residual. The flat tail goes through
+// mix->stage (launch_flat_ingest first, launch_flat_round last), the iterations are compress_wide's
+// (with psgd_aggregate_comm's collectives), the final pass is launch_wide_apply_mix
+int aggregate_wide_mix_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
+                           void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs& mix);
 
 }  // namespace psgd
 

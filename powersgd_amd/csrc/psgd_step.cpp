@@ -219,7 +219,10 @@ int compress_wide(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hi
     return PSGD_OK;
 }
 
-int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s) {
+// `mix` (psgd_aggregate_mixed_wide[_comm]): `grads` the fp32 residual, `out` bf16: the same arguments
+// to k_wide_apply_mix
+int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s,
+                    bool mix = false) {
     if (int st = refresh_pointers(p, grads, s)) return st;
     const int I = p->iters;
     WideArgs a{};
@@ -237,7 +240,8 @@ int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, i
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     if (int st = timing_begin(p, s, &ev, true)) return st;
     TimedScope ts(ev);
-    PSGD_HIP(launch_wide_apply(p->dtype, p->rbucket, a, int(p->wide_apply.size()), s));
+    if (mix) PSGD_HIP(launch_wide_apply_mix(p->rbucket, a, int(p->wide_apply.size()), s, nullptr));
+    else PSGD_HIP(launch_wide_apply(p->dtype, p->rbucket, a, int(p->wide_apply.size()), s));
     return PSGD_OK;
 }
 
@@ -695,6 +699,28 @@ int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_
     d.fl = has_flat && ride ? &fa : nullptr;
     if (int st = decompress_impl(p, grads, out, step, world, s, d)) return st;
     if (has_flat && !ride) PSGD_HIP(dst ? launch_flat_round_dst(fa, *mix, dst->unc_dst, s) : launch_flat_round(fa, *mix, s));
+    return PSGD_OK;
+}
+
+int psgd::aggregate_wide_mix_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f,
+                                 void* const* unc, void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs& mix) {
+    const int world = comm ? comm_world(comm) : 1;
+    FlatArgs fa{};
+    if (f) {  // stage = (x + float(g)) / W, x = g = +0.0: ahead of every collective
+        if (int st = flat_args(f, unc, flat_out, world, s, &fa)) return st;
+        PSGD_HIP(launch_flat_ingest(fa, mix, s));
+    }
+    for (int it = 0; it < p->iters; ++it) {
+        if (int st = compress_impl(p, grads, step, it, s, StepCtx{})) return st;
+        if (!comm) continue;
+        const bool e = p->even(step, it);
+        const bool last = it == p->iters - 1;
+        if (int st = comm_allreduce(comm, e ? p->Q : p->P, size_t(e ? p->qtot : p->ptot), last && f ? mix.stage : nullptr,
+                                    last && f ? size_t(f->total) : 0, s))
+            return st;
+    }
+    if (int st = decompress_wide(p, grads, out, step, world, s, true)) return st;
+    if (f) PSGD_HIP(launch_flat_round(fa, mix, s));
     return PSGD_OK;
 }
 

@@ -17,17 +17,18 @@ next backward accumulates fresh gradients only. Cost against ``PowerSGD`` on the
 gradients: the two element-wise passes, an fp32 codec step, 4 bytes of state per parameter.
 
 ``fused=True`` runs the same step as ONE library call (psgd_aggregate_mixed, include/psgd.h)
-wherever it applies (one process, a compressing step, rank bucket 1 / 2 / 4 / 16 / 32; rank bucket
-8 and ranks above 32 run the three stages): the codec's final
+wherever it applies (one process, a compressing step, rank bucket 1 / 2 / 4 / 16 / 32, or ranks
+33-128 through psgd_aggregate_mixed_wide; rank bucket 8 runs the three stages): the codec's final
 pass stores the bf16 averages itself (no GATHER pass), and where a step is one gradient pass
 (one iteration per step, odd steps) that pass also ingests the bf16 gradients (no ADD pass; on the
 other steps the library launches the ADD). In a process group that runs over the library's own RCCL
 communicator the one call is psgd_aggregate_mixed_comm: the output fold on every step, the ADD
 always a launch of the library's, the uncompressed tensors all-reduced in fp32 and rounded in the
-final launch. With ``PSGD_COMM=ipc`` it is psgd_aggregate_mixed_ipc over the codec's IPC exchange
-session: the same output fold, and the last exchange stores the uncompressed tensors' averages as
-bf16 itself. Bit for bit the three-stage flow above; every other case (``PSGD_COMM=torch``, gloo
-without the IPC exchange, an ineligible plan) runs it.
+final launch (ranks 33-128: psgd_aggregate_mixed_wide_comm). With ``PSGD_COMM=ipc`` it is
+psgd_aggregate_mixed_ipc over the codec's IPC exchange session: the same output fold, and the last
+exchange stores the uncompressed tensors' averages as bf16 itself (rank buckets up to 32; ranks
+33-128 run the three stages there). Bit for bit the three-stage flow above; every other case
+(``PSGD_COMM=torch``, gloo without the IPC exchange, an ineligible plan) runs it.
 """
 from __future__ import annotations
 
@@ -102,6 +103,7 @@ class Fp32ResidualPowerSGD(Aggregator, metaclass=_ClipKeyword):
             self._ws.append(ws)
         self._slab = _output_slab(shapes, _lib.PSGD_BF16, self._dev_index)
         self._fused_state = None  # built by the first fused step
+        self._wide_ok = None      # _wide_plan's answer, asked once
 
     @property
     def step_counter(self) -> int:
@@ -194,12 +196,30 @@ class Fp32ResidualPowerSGD(Aggregator, metaclass=_ClipKeyword):
         if inner.step_counter + 1 <= self.config.start_compressing_after_num_steps:
             return False
         plan = inner._powersgd._plan
+        if self._fused_wide():
+            return True
         if is_distributed():
             world = self._fused_world()
             if world is None:
                 return False
             return plan.mixed_folds_comm(0, world)[1] == 1 and plan.mixed_folds_comm(1, world)[1] == 1
         return plan.mixed_folds(0)[1] == 1 and plan.mixed_folds(1)[1] == 1
+
+    def _fused_wide(self) -> bool:
+        """The one-call form of a wide plan (ranks 33-128) serves the step: psgd_aggregate_mixed_wide in
+        one process, psgd_aggregate_mixed_wide_comm over the library's communicator. The IPC exchange
+        has no wide one-call form (the three stages)."""
+        if not self._wide_plan():
+            return False
+        return not is_distributed() or self._fused_comm() is not None
+
+    def _wide_plan(self) -> bool:
+        """The plan is one psgd_aggregate_mixed_wide[_comm] serves (psgd_plan_mixed_wide_ok: a property
+        of the plan on this device, whatever the world size): asked once."""
+        if self._wide_ok is None:
+            plan = self.inner._powersgd._plan
+            self._wide_ok = plan.is_wide() and plan.mixed_wide_ok(1) == 1
+        return self._wide_ok
 
     def fused_folds(self):
         """``(fold_in, fold_out)`` of the NEXT ``aggregate`` call: 1 where the ingest of the bf16
@@ -212,6 +232,8 @@ class Fp32ResidualPowerSGD(Aggregator, metaclass=_ClipKeyword):
         if not (self.fused and self._fused_applies()):
             return (0, 0)
         codec = self.inner._powersgd
+        if self._fused_wide():  # the ADD is a launch of its own, the final pass stores bf16
+            return (0, 1)
         if is_distributed():
             return codec._plan.mixed_folds_comm(codec.step_counter, self._fused_world())
         return codec._plan.mixed_folds(codec.step_counter)
@@ -246,7 +268,10 @@ class Fp32ResidualPowerSGD(Aggregator, metaclass=_ClipKeyword):
             kw = dict(flat=inner._unc.plan, unc_bf16=st["grads"].unc_addr(), unc_residual=inner._table.unc_addr(),
                       flat_out=st["unc_slab"].data_ptr())
             outs = outs + unc
-        if ipc:
+        if self._wide_plan() and (comm is not None or not is_distributed()):  # _fused_wide, `comm` in hand
+            codec._plan.aggregate_mixed_wide(st["grads"].comp_addr(), inner._table.comp_addr(), st["comp_slab"].data_ptr(),
+                                             codec.step_counter, stream, comm=comm, **kw)
+        elif ipc:
             codec._plan.aggregate_mixed_ipc(st["grads"].comp_addr(), inner._table.comp_addr(),
                                             st["comp_slab"].data_ptr(), codec.step_counter, stream, **kw)
         elif comm is not None:

@@ -10,6 +10,12 @@ import sys
 src = sys.argv[1]
 filt = sys.argv[2] if len(sys.argv) > 2 else ""
 EXTRA = os.environ.get("EXTRA", "").split()
+# the unit's own flags from the Makefile ("$(OBJDIR)/<source>.o: CXXFLAGS += ...")
+if os.path.exists("Makefile"):
+    for line in open("Makefile"):
+        m = re.match(r"\$\(OBJDIR\)/" + re.escape(os.path.basename(src)) + r"\.o:\s*CXXFLAGS\s*\+=\s*(.*)", line)
+        if m:
+            EXTRA += m.group(1).split()
 cmd = ["/opt/rocm/bin/hipcc", *EXTRA, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I../../include",
        "-x", "hip", "-c", src, "-o", "/tmp/_regs.o", "-Rpass-analysis=kernel-resource-usage"]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr

@@ -165,15 +165,13 @@ int psgd::ipc_check(const psgd_plan* p, int64_t step) {
 // then k_xchg (flag, bounded wait for the peers' flags, rank-order SUM into the state buffer; the
 // last one also sums the uncompressed tensors packed /W into flat_out), then the output pass.
 // Nothing leaves the stream: no host barrier, no host synchronisation.
-// `mix` (psgd_aggregate_mixed_ipc): the flat tail is ingest-packed into the slot in a launch of its
-// own first (flat_ingest_item, the slot as its stage), the last exchange is k_xchg_mix (the flat
-// sums stored as bf16 into `flat_out`) and the output pass runs its bf16-output instance with no
-// flat items. `mix` and `dst` (psgd_aggregate_mixed_ipc_dst): `grads` already holds residual +
-// gradients, so the flat tail is packed as without `mix`, and both stores follow dst's tables.
-// Every other launch, flag and epoch is the same in the three forms.
-int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
-                            void* flat_out, hipStream_t s, const MixArgs* mix, const MixDst* dst,
-                            const DirectDst* fdst) {
+// The flat tail by the sink's properties: it lives in the exchange slot, ingest-packed there in a
+// launch of its own first by an ingesting sink (flat_ingest_item, the slot as its stage), packed as
+// above by every other. The last exchange sums it into the sink's fp32 buffer, or for a bf16 sink is
+// k_xchg_mix, which stores the sums as bf16 where the averages belong (no stage). Only a copying
+// sink's items ride in the output pass. Every other launch, flag and epoch is the same for every sink.
+int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, int64_t step, psgd_flat* f, void* const* unc, hipStream_t s,
+                            const OutSink& sink) {
     const bool has_flat = f != nullptr;
     const int world = p->ipc_world;
     const int last = p->iters - 1;
@@ -181,13 +179,13 @@ int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t
     // x / W into this rank's last slot: inside the first even product's launch when the step
     // starts even, else its own launch
     FlatArgs fa{};
-    const bool ingest = mix && !dst;
+    const bool ingest = sink.ingests();
     const bool fold = has_flat && !ingest && p->even(step, 0) && !p->wide();  // wide products carry no flat pack
     float* flat_slot = p->xslot(step, last) + p->ipc_flat_off;
     if (has_flat) {
         if (int st = flat_args(f, unc, flat_slot, world, s, &fa)) return st;
         if (ingest) {
-            MixArgs in = *mix;
+            MixArgs in = sink.mix();
             in.stage = flat_slot;  // its stores are write-through (kStAuxSlot), as the pack's
             PSGD_HIP(launch_flat_ingest(fa, in, s));
         } else if (!fold) {
@@ -229,7 +227,7 @@ int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t
         xa.n = e ? p->qtot : p->ptot;
         const bool tail = it == last && has_flat;
         if (tail) {
-            xa.flat_dst = mix ? nullptr : fdst ? fdst->stage : static_cast<float*>(flat_out);
+            xa.flat_dst = sink.bf16 ? nullptr : sink.sums();
             xa.flat_off = p->ipc_flat_off;
             xa.nflat = f->total;
         }
@@ -242,14 +240,14 @@ int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t
         xa.rank = p->ipc_rank;
         xa.err = p->xerr_dev;
         xa.err_dev = reinterpret_cast<int32_t*>(static_cast<char*>(p->ipc_buf) + kXchgErrOff);
-        if (tail && mix) {  // the summed flat tail goes out as bf16 (the last iteration never takes the item form)
+        if (tail && sink.bf16) {  // the summed flat tail goes out as bf16 (the last iteration never takes the item form)
             XchgMixArgs xm{};
             xm.entries = fa.entries;
             xm.items = fa.items;
             xm.nitems = fa.nitems;
-            xm.flat_out = dst ? nullptr : flat_out;
-            xm.unc_dst = dst ? dst->unc_dst : nullptr;
-            PSGD_HIP(launch_xchg_mix(xa, xm, dst != nullptr, s));
+            xm.flat_out = sink.tables ? nullptr : sink.flat_out;
+            xm.unc_dst = sink.tables ? sink.unc_dst : nullptr;
+            PSGD_HIP(launch_xchg_mix(xa, xm, sink.tables, s));
         } else if (p->ipc_two_shot(e ? 1 : 0)) {
             // reduce-scatter on the first epoch of the step, all-gather (and the flat tail) on the
             // second, as two launches: the kernel boundary drains the in-place shard stores
@@ -261,16 +259,12 @@ int psgd::aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t
             PSGD_HIP(launch_xchg(xa, s));
         }
     }
-    // the output pass: the route and the term sources are the same with and without `mix` (fuse and
+    // the output pass: the route and the term sources are the same for every sink (fuse and
     // write_out clear: the earlier iterations' summed factors in history slot 2, where the item form
-    // of k_xchg or k_orth's save left them); no flat items ride in it
-    StepCtx d = mix ? comm_out_ctx(mix, dst) : StepCtx{};
-    if (fdst) {  // psgd_aggregate_ipc_dst: the last exchange summed the flat tail into fdst->stage; its
-                 // copy items ride in the output pass's destination-table instance
-        d.fdst = fdst;
-        d.fl = has_flat ? &fa : nullptr;
-    }
-    return decompress_impl(p, grads, out, step, world, s, d);
+    // of k_xchg or k_orth's save left them)
+    StepCtx d = out_ctx(&sink);
+    d.fl = has_flat && sink.copies() ? &fa : nullptr;
+    return decompress_impl(p, grads, sink.out, step, world, s, d);
 }
 
 extern "C" {
@@ -494,8 +488,10 @@ int psgd_aggregate_ipc(psgd_plan* p, void* const* grads, void* out, int64_t step
         if (f->total > p->ipc_flat_cap) return fail(PSGD_ERR_VALUE, "flat tensors exceed the exchange buffer (psgd_ipc_create)");
     }
     DevScope scope(p->device);
-    return aggregate_ipc_ctx(p, grads, out, step, has_flat ? f : nullptr, unc, flat_out, static_cast<hipStream_t>(stream),
-                             nullptr, nullptr);
+    OutSink sink;
+    sink.out = out;
+    sink.flat_out = flat_out;
+    return aggregate_ipc_ctx(p, grads, step, has_flat ? f : nullptr, unc, static_cast<hipStream_t>(stream), sink);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 // scale pass, which reads the coefficient on the device and returns at once when nothing is
 // clipped. No host synchronisation.
 // psgd_clip_dst / psgd_plan_clip_dst_ok: the same after a direct-store completion
-// (psgd_direct.cpp): the factor form and the stream sum over the plan's staged flat tail, then the
+// (psgd_onecall.cpp): the factor form and the stream sum over the plan's staged flat tail, then the
 // scale pass through the destination tables (k_norm_scale_dst).
 #include <cmath>
 #include <cstdlib>
@@ -14,7 +14,7 @@
 #include "psgd_norm.h"
 #include "psgd_plan.h"
 
-// State of its own like psgd_plan::Mixed / Direct: one device allocation made by the first call,
+// State of its own like psgd_plan::Side: one device allocation made by the first call,
 // freed with the plan; the caller's workspace carve does not move.
 struct psgd_plan::Norm {
     std::vector<NormItem> items;

@@ -1,0 +1,478 @@
+// The one-call steps that store their averages through an OutSink (psgd_plan.h), and their queries
+// (include/psgd.h). Each is DEFINED as a sequence of the plain calls and equal to it bit for bit:
+//   bf16 sinks   the fp32 codec on an fp32 error-feedback residual fed by bf16 gradients:
+//                  residual += float(g); g = +0.0   (psgd_runs_add_list, zero_source: "the ADD")
+//                  psgd_aggregate[_flat] / psgd_aggregate_comm / psgd_aggregate_ipc on the residual
+//                  out = bf16(averages)             (psgd_runs_gather)
+//                psgd_aggregate_mixed[_flat] at world size 1, _comm over a communicator, _ipc over
+//                the plan's exchange session, _wide[_comm] on a wide plan (ranks 33-128). The ADD is
+//                the first launch, but on the steps of psgd_aggregate_mixed whose only gradient pass
+//                is the single-pass k_final_odd (I = 1, odd step, ranks 1 / 2), which ingests there.
+//                _comm_dst / _ipc_dst: the DDP hook's form. The residual already holds residual +
+//                gradients (the hook adds each bucket on arrival): no ADD, and the final pass stores
+//                each tensor's bf16 average at the tensor's own destination.
+//   fp32 tables  psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst, the default DDP hook's completion:
+//                psgd_aggregate_comm (psgd_aggregate_ipc) on the gradients with every fp32 average
+//                stored at the tensor's own destination, so no slab is written and no gather runs.
+// Every entry is a descriptor (Entry) and its arguments (Call): one preamble runs the checks in the
+// entry's documented order, one body makes the side state, asks admission (a refusal launches
+// nothing), builds the sink and hands it to the step driver of the entry's transport.
+#include <string>
+
+#include "psgd_plan.h"
+
+namespace {
+
+using Adm = psgd_plan::Admission;
+
+struct Entry {
+    const char* name;  // for messages
+    enum Via { World1, Comm, Xchg } via;
+    bool wide, tables, bf16;
+    Adm::Kind kind() const { return !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense; }
+};
+
+// The arguments by role. `state`: the fp32 tensors the codec runs on (a bf16 sink: the residual; else
+// the gradients); `peer`: per tensor the bf16 gradient (dense sinks) or the destination (tables).
+// `unc_state` / `unc_peer`: the same of the flat plan's tensors. `out` / `flat_out`: dense sinks.
+struct Call {
+    psgd_plan* p;
+    void* const* state;
+    void* const* peer;
+    void* out;
+    int64_t step;
+    psgd_flat* f;
+    void* const* unc_state;
+    void* const* unc_peer;
+    void* flat_out;
+    psgd_comm* comm;
+    void* stream;
+};
+
+// The plans an entry serves, by shape. bf16 sinks: fp32, one bucket, rank buckets 1 / 2 / 4 (VALU
+// tiles) and 16 / 32 (matrix-core tiles, psgd_mixed_mfma.hip), not 8 (the VALU tile whose
+// register-cached two-set instances sit at the scratch edge); the wide entries: what those refuse by
+// rank. fp32 tables: fp32, one bucket, not wide
+const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code) {
+    *code = PSGD_ERR_VALUE;
+    const int rb = p->rbucket;
+    if (!bf16) {
+        if (p->dtype != PSGD_F32) {
+            *code = PSGD_ERR_DTYPE;
+            return "psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst take an fp32 plan";
+        }
+        if (p->wide()) return "psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst serve rank buckets 1 to 32";
+        if (p->spans.size() > 1) return "psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst take a plan of one bucket";
+    } else if (wide) {
+        if (p->dtype != PSGD_F32)
+            return "psgd_aggregate_mixed_wide takes an fp32 plan (the fp32 residual of bf16 gradients)";
+        if (!p->wide())
+            return "psgd_aggregate_mixed_wide serves ranks 33-128 (psgd_aggregate_mixed: rank buckets 1, 2, 4, 16 and 32)";
+        if (p->spans.size() > 1) return "psgd_aggregate_mixed_wide takes a plan of one bucket";
+    } else {
+        if (p->dtype != PSGD_F32) return "psgd_aggregate_mixed takes an fp32 plan (the fp32 residual of bf16 gradients)";
+        if (p->wide() || !(rb == 1 || rb == 2 || rb == 4 || rb == 16 || rb == 32))
+            return "psgd_aggregate_mixed serves rank buckets 1, 2, 4, 16 and 32 (not 8, not ranks above 32)";
+        if (p->spans.size() > 1) return "psgd_aggregate_mixed takes a plan of one bucket";
+    }
+    return nullptr;
+}
+
+// ------------------------------------------------------------------ admission ------
+// One cell: the instance the final pass of parity `par` would launch for a sink of `kind` under a
+// communicator kind, asked with ntiles = 0 through the launch functions the drivers use. NoComm is
+// aggregate_ctx's context (the fused final pass where the step has one); Bf16Ingest its single-pass
+// final kernel with the ingest fold (false where the step's first pass is another one). A wide
+// plan's only sink instance is k_wide_apply_mix<rbucket> (shared terms at world size 1)
+bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
+    OutSink sink;
+    sink.bf16 = kind != Adm::F32Tables;
+    sink.tables = kind == Adm::Bf16Tables || kind == Adm::F32Tables;
+    const int world = comm == Adm::Many ? 2 : 1;
+    int w = 0;
+    hipError_t e = hipErrorInvalidValue;
+    if (p->wide()) {
+        WideArgs a{};
+        a.shared = world == 1;
+        if (kind == Adm::Bf16Dense) e = launch_wide_apply_mix(p->rbucket, a, 0, nullptr, &w);
+    } else if (comm == Adm::NoComm) {
+        StepCtx c = world1_ctx(out_ctx(&sink));
+        c.mix_in = kind == Adm::Bf16Ingest && p->mix_ingest_on;
+        const IterRoute r = p->route(par, kind == Adm::Bf16Ingest ? 0 : p->iters - 1, c);
+        ApplyArgs aa{};
+        if (r.pass == IterRoute::PassFinal && (kind != Adm::Bf16Ingest || r.ingest))
+            e = launch_final_pass(p, r, FinalArgs{}, &sink, 0, nullptr, &w);
+        else if (kind != Adm::Bf16Ingest)
+            e = launch_out_pass(p, p->out_route(par, 1, c), aa, &sink, 0, nullptr, &w);
+    } else {
+        ApplyArgs aa{};
+        e = launch_out_pass(p, p->out_route(par, world, out_ctx(&sink)), aa, &sink, 0, nullptr, &w);
+    }
+    return e == hipSuccess && w >= 2;
+}
+
+// Both parities of (kind, comm) are admitted on the plan's current tiling; asked once per key. The
+// key covers every plan field the routes read that can change after creation (a re-tiling: fin_ok,
+// fin_proj, oe_ok, fin_smax, out_nt); rank bucket, iterations and the knobs are fixed
+bool admitted(psgd_plan* p, Adm::Kind kind, Adm::Comm comm) {
+    Adm& a = p->adm;
+    const uint64_t key = uint64_t(p->fin_ok) | uint64_t(p->fin_proj) << 1 | uint64_t(p->oe_ok) << 2 |
+                         uint64_t(uint32_t(p->fin_smax)) << 8 | uint64_t(uint32_t(p->out_nt)) << 40;
+    if (a.key != key) {
+        a = Adm{};
+        a.key = key;
+    }
+    if (!a.asked[kind][comm]) {
+        a.asked[kind][comm] = true;
+        for (int par = 0; par < 2; ++par) a.ok[kind][comm][par] = ask(p, kind, comm, par);
+    }
+    return a.ok[kind][comm][0] && a.ok[kind][comm][1];
+}
+
+// A communicator's world size is known only at the call: the bf16 sinks of the narrow plans answer
+// per communicator kind; the wide entries and the fp32 tables are eligible as a whole plan or not
+bool eligible(psgd_plan* p, const Entry& e, int world) {
+    if (e.via == Entry::World1 && !e.wide) return admitted(p, e.kind(), Adm::NoComm);
+    if (e.wide || !e.bf16) return admitted(p, e.kind(), Adm::Many) && admitted(p, e.kind(), Adm::One);
+    return admitted(p, e.kind(), world == 1 ? Adm::One : Adm::Many);
+}
+
+// psgd_aggregate_mixed's ingest fold on `step`: its only gradient pass is the single-pass final
+// kernel and that instance is admitted (after eligible())
+bool ingest_fold(psgd_plan* p, int64_t step) {
+    (void)admitted(p, Adm::Bf16Ingest, Adm::NoComm);
+    return p->adm.ok[Adm::Bf16Ingest][Adm::NoComm][step & 1];
+}
+
+// A query: admission is a property of this build's kernels on the device, cached in the plan per
+// tiling. A plan with no device yet answers for the current device and keeps nothing
+template <typename Read>
+int query(const psgd_plan* plan, Read read) {
+    psgd_plan* p = const_cast<psgd_plan*>(plan);
+    DevScope scope(p->device);
+    read(p);
+    if (!p->bound) p->adm = Adm{};
+    return PSGD_OK;
+}
+
+// ------------------------------------------------------------------ side state ------
+// made once, by the first call on a bound plan: the tables of the plan's tensors and, for the bf16
+// sinks, the run-table ADD with its workspace
+int ensure(psgd_plan* p, psgd_plan::Side*& slot, bool add) {
+    if (slot) return PSGD_OK;
+    slot = new psgd_plan::Side();
+    const size_t nt = p->shapes.size();
+    if (int st = slot->per.room(nt, nullptr)) return st;
+    if (!add) return PSGD_OK;
+    std::vector<int64_t> zero(nt, 0), numel(nt, 1);
+    std::vector<int32_t> idx(nt);
+    for (size_t i = 0; i < nt; ++i) {
+        idx[i] = int32_t(i);
+        for (int64_t x : p->shapes[i]) numel[i] *= x;
+    }
+    if (int st = psgd_runs_create_mixed(zero.data(), idx.data(), zero.data(), numel.data(), idx.data(), int32_t(nt),
+                                        int32_t(nt), int32_t(nt), PSGD_BF16, PSGD_F32, &slot->add))
+        return st;
+    int64_t rb = 0;
+    if (int st = psgd_runs_workspace_bytes(slot->add, &rb)) return st;
+    PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&slot->add_ws), size_t(std::max<int64_t>(rb, 1))));
+    return psgd_runs_bind(slot->add, p->device, slot->add_ws);
+}
+
+void release(psgd_plan::Side*& slot) {
+    if (!slot) return;
+    if (slot->add) (void)psgd_runs_destroy(slot->add);
+    if (slot->add_ws) (void)hipFree(slot->add_ws);
+    delete slot;
+    slot = nullptr;
+}
+
+// ------------------------------------------------------------------ entries ------
+// The checks before any device work, in the entry's documented order (include/psgd.h): the exchange
+// entries report the argument errors before the plan's state, the others "not bound" before the
+// range check; the fp32 tables the plan's shape before the flat plan, the bf16 sinks after it.
+// Leaves c.f null where there is no flat tail
+int preamble(const Entry& e, Call& c) {
+    const psgd_plan* p = c.p;
+    const bool args = p && c.state && c.peer && (e.tables || c.out) && (e.via != Entry::Comm || c.comm);
+    if (e.via == Entry::Xchg) {
+        if (!args) return fail(PSGD_ERR_VALUE, "null argument");
+        if (c.step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
+        if (!p->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
+    } else if (int st = check_call(args, p && p->bound, c.step >= 0, "step out of range")) {
+        return st;
+    }
+    if (!e.tables)
+        if (int st = check_out(c.out)) return st;
+    int code = PSGD_ERR_VALUE;
+    const char* why = ineligible(p, e.bf16, e.wide, &code);
+    if (why && !e.bf16) return fail(code, why);
+    if (!c.f || c.f->total == 0) c.f = nullptr;
+    if (const psgd_flat* f = c.f) {
+        const bool type_ok = f->dtype == PSGD_F32 && f->device == p->device;
+        std::string msg;  // built for the refusal only: nothing is allocated on a call that passes
+        if (!type_ok)
+            msg = std::string(e.name) + " takes an fp32 flat plan" + (e.bf16 ? " (the uncompressed tensors' residual)" : "") +
+                  " on the codec's device";
+        if (int st = check_flat(f, c.unc_state && c.unc_peer && (e.tables || c.flat_out), type_ok, PSGD_ERR_VALUE, msg.c_str()))
+            return st;
+        if (!e.bf16)
+            for (int32_t i = 0; i < f->count; ++i)
+                if (!c.unc_state[i] || !c.unc_peer[i]) return fail(PSGD_ERR_VALUE, "null uncompressed tensor pointer");
+    }
+    if (why) return fail(code, why);
+    // every tensor's two pointers: the bf16 side (gradients, or destinations like them) 2-byte
+    // aligned and the fp32 residual 4-byte; fp32 destinations 4-byte
+    const uintptr_t al = e.bf16 ? 2 : 4;
+    const char* al_msg = e.bf16 ? "bf16 gradients must be 2-byte aligned" : "fp32 destinations must be 4-byte aligned";
+    for (size_t i = 0; i < p->shapes.size(); ++i) {
+        if (!c.state[i] || !c.peer[i]) return fail(PSGD_ERR_VALUE, "null gradient pointer");
+        if (reinterpret_cast<uintptr_t>(c.peer[i]) % al) return fail(PSGD_ERR_LAYOUT, al_msg);
+        if (e.bf16 && reinterpret_cast<uintptr_t>(c.state[i]) % 4)
+            return fail(PSGD_ERR_LAYOUT, "the fp32 residual must be 4-byte aligned");
+    }
+    if (c.f && !e.bf16)
+        for (int32_t i = 0; i < c.f->count; ++i)
+            if (reinterpret_cast<uintptr_t>(c.unc_peer[i]) % al) return fail(PSGD_ERR_LAYOUT, al_msg);
+    if (e.via == Entry::Xchg) {
+        if (int st = ipc_check(p, c.step)) return st;
+        if (c.f && c.f->total > p->ipc_flat_cap)
+            return fail(PSGD_ERR_VALUE, "flat tensors exceed the exchange buffer (psgd_ipc_create)");
+    }
+    return PSGD_OK;
+}
+
+// Past the checks. Everything that can refuse comes before the first launch; *refused: the plan has
+// no admitted instance (nothing launched, no collective issued: a communicator stays usable)
+int body(const Entry& e, const Call& c, bool* refused) {
+    psgd_plan* p = c.p;
+    psgd_flat* f = c.f;
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    DevScope scope(p->device);
+    psgd_plan::Side*& slot = e.bf16 ? p->mixed : p->direct;
+    if (int st = ensure(p, slot, e.bf16)) return st;
+    psgd_plan::Side& m = *slot;
+    // the tiling the step will run on: the state's alignment decides the vector layout (a
+    // destination's only picks the store form, in the kernel), and admission asks about that tiling.
+    // The wide kernels test each tensor's alignment themselves
+    if (!e.wide)
+        if (int st = refresh_pointers(p, c.state, s)) return st;
+    const int world = e.via == Entry::Comm ? comm_world(c.comm) : e.via == Entry::Xchg ? p->ipc_world : 1;
+    if (!eligible(p, e, world)) {
+        *refused = true;
+        const char* what = e.wide     ? "k_wide_apply_mix for this plan's rank bucket"
+                           : e.tables ? "destination-table instance of this plan's final pass"
+                                      : "bf16-output instance of this plan's final pass";
+        return fail(PSGD_ERR_VALUE, std::string(e.name) + ": no admitted " + what + " (two waves per SIMD, no scratch)");
+    }
+    const bool ingest = e.via == Entry::World1 && !e.wide && ingest_fold(p, c.step);
+    OutSink sink;
+    sink.bf16 = e.bf16;
+    sink.tables = e.tables;
+    sink.out = c.out;
+    sink.flat_out = c.flat_out;
+    if (f) {
+        if (int st = m.unc.room(size_t(f->count), s)) return st;
+        if (e.bf16)
+            for (int32_t i = 0; i < f->count; ++i)
+                if (!c.unc_peer[i] || !c.unc_state[i]) return fail(PSGD_ERR_VALUE, "null uncompressed tensor pointer");
+        // a collective sums fp32: the flat tail is staged, but where it lives in the exchange slot
+        // and k_xchg_mix stores its sums as bf16, or rides in the world-size-1 final pass
+        if (!e.bf16 || e.via == Entry::Comm || e.wide) {
+            if (int st = m.unc.stage_room(size_t(f->total), s)) return st;
+            sink.stage = m.unc.stage;
+        }
+        TableCache& t = e.tables ? m.unc.b : m.unc.a;
+        PSGD_HIP(t.select(c.unc_peer, s));
+        (e.tables ? sink.unc_dst : sink.unc_src) = t.table();
+    }
+    if (e.tables) {
+        PSGD_HIP(m.per.b.select(c.peer, s));
+        sink.dst = m.per.b.table();
+    } else if (ingest) {
+        PSGD_HIP(m.per.a.select(c.peer, s));
+        sink.src = m.per.a.table();
+    } else if (int st = psgd_runs_add_list(m.add, c.peer, c.state, 1, s)) {
+        return st;
+    }
+    if (e.via == Entry::Xchg) return aggregate_ipc_ctx(p, c.state, c.step, f, c.unc_state, s, sink);
+    if (e.via == Entry::Comm || e.wide) return aggregate_comm_ctx(p, c.state, c.step, f, c.unc_state, c.comm, s, sink);
+    FlatArgs fa{};
+    StepCtx x = out_ctx(&sink);
+    x.mix_in = ingest;
+    x.out = c.out;
+    if (f) {
+        if (int st = flat_args(f, c.unc_state, c.flat_out, 1, s, &fa)) return st;
+        x.fl = &fa;
+    }
+    return aggregate_ctx(p, c.state, c.step, s, x);
+}
+
+int run(const Entry& e, Call c) {
+    if (int st = preamble(e, c)) return st;
+    if (e.via == Entry::Comm) return with_comm(c.comm, [&](bool* refused) { return body(e, c, refused); });
+    bool refused = false;
+    return body(e, c, &refused);
+}
+
+// what the queries check of their arguments (`world` 1 where the query takes none)
+int query_args(bool ptrs, int64_t step, int32_t world) {
+    if (!ptrs) return fail(PSGD_ERR_VALUE, "null argument");
+    if (step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
+    if (world < 1) return fail(PSGD_ERR_VALUE, "world size must be >= 1");
+    return PSGD_OK;
+}
+
+const Entry kMixedFlat{"psgd_aggregate_mixed_flat", Entry::World1, false, false, true};
+const Entry kMixedComm{"psgd_aggregate_mixed_comm", Entry::Comm, false, false, true};
+const Entry kMixedIpc{"psgd_aggregate_mixed_ipc", Entry::Xchg, false, false, true};
+const Entry kMixedWide{"psgd_aggregate_mixed_wide", Entry::World1, true, false, true};
+const Entry kMixedWideComm{"psgd_aggregate_mixed_wide_comm", Entry::Comm, true, false, true};
+const Entry kMixedCommDst{"psgd_aggregate_mixed_comm_dst", Entry::Comm, false, true, true};
+const Entry kMixedIpcDst{"psgd_aggregate_mixed_ipc_dst", Entry::Xchg, false, true, true};
+const Entry kCommDst{"psgd_aggregate_comm_dst", Entry::Comm, false, true, false};
+const Entry kIpcDst{"psgd_aggregate_ipc_dst", Entry::Xchg, false, true, false};
+
+}  // namespace
+
+void psgd::side_release(psgd_plan* p) {
+    release(p->mixed);
+    release(p->direct);
+}
+
+bool psgd::direct_shape_ok(const psgd_plan* p) {
+    int code = 0;
+    return ineligible(p, false, false, &code) == nullptr;
+}
+
+int psgd::direct_select(psgd_plan* p, void* const* dst, const psgd_flat* f, void* const* unc_dst, hipStream_t s,
+                        DirectDst* t) {
+    if (f) {  // checked before the state is made: a refusal leaves nothing behind
+        const psgd_plan::Side* m = p->direct;
+        if (!m || !m->unc.stage || m->unc.stage_cap < size_t(f->total) || m->unc.cap < size_t(f->count))
+            return fail(PSGD_ERR_STATE, "the flat tail is not staged (call after psgd_aggregate_comm_dst / _ipc_dst)");
+    }
+    if (int st = ensure(p, p->direct, false)) return st;
+    psgd_plan::Side& m = *p->direct;
+    if (f) {
+        if (int st = m.unc.room(size_t(f->count), s)) return st;  // within its capacity: a re-bind at the most
+        PSGD_HIP(m.unc.b.select(unc_dst, s));
+        t->unc_dst = m.unc.b.table();
+        t->stage = m.unc.stage;
+    }
+    PSGD_HIP(m.per.b.select(dst, s));
+    t->dst = m.per.b.table();
+    return PSGD_OK;
+}
+
+extern "C" {
+
+int psgd_plan_mixed_folds(const psgd_plan* plan, int64_t step, int32_t* fold_in, int32_t* fold_out) {
+    if (int st = query_args(plan && fold_in && fold_out, step, 1)) return st;
+    *fold_in = *fold_out = 0;
+    int code = 0;
+    if (ineligible(plan, true, false, &code)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) {
+        *fold_out = eligible(p, kMixedFlat, 1) ? 1 : 0;
+        *fold_in = *fold_out && ingest_fold(p, step) ? 1 : 0;
+    });
+}
+
+int psgd_plan_mixed_folds_comm(const psgd_plan* plan, int64_t step, int32_t world, int32_t* fold_in,
+                               int32_t* fold_out) {
+    if (int st = query_args(plan && fold_in && fold_out, step, world)) return st;
+    *fold_in = *fold_out = 0;  // no ingest fold in this form: the ADD is always a launch of its own
+    int code = 0;
+    if (ineligible(plan, true, false, &code)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *fold_out = eligible(p, kMixedComm, world) ? 1 : 0; });
+}
+
+int psgd_plan_mixed_folds_dst(const psgd_plan* plan, int64_t step, int32_t world, int32_t* fold_out) {
+    if (int st = query_args(plan && fold_out, step, world)) return st;
+    *fold_out = 0;
+    int code = 0;
+    if (ineligible(plan, true, false, &code)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *fold_out = eligible(p, kMixedCommDst, world) ? 1 : 0; });
+}
+
+int psgd_plan_mixed_wide_ok(const psgd_plan* plan, int32_t world, int32_t* ok) {
+    if (int st = query_args(plan && ok, 0, world)) return st;
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, true, true, &code)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kMixedWideComm, world) ? 1 : 0; });
+}
+
+int psgd_plan_dst_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, false, false, &code)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kCommDst, world) ? 1 : 0; });
+}
+
+int psgd_aggregate_mixed_flat(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,
+                              psgd_flat* f, void* const* unc_bf16, void* const* unc_residual, void* flat_out_bf16,
+                              void* stream) {
+    return run(kMixedFlat, Call{p, residual, grads_bf16, out_bf16, step, f, unc_residual, unc_bf16, flat_out_bf16,
+                                nullptr, stream});
+}
+
+int psgd_aggregate_mixed(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,
+                         void* stream) {
+    return psgd_aggregate_mixed_flat(p, grads_bf16, residual, out_bf16, step, nullptr, nullptr, nullptr, nullptr,
+                                     stream);
+}
+
+int psgd_aggregate_mixed_comm(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16,
+                              int64_t step, psgd_flat* f, void* const* unc_bf16, void* const* unc_residual,
+                              void* flat_out_bf16, psgd_comm* comm, void* stream) {
+    return run(kMixedComm, Call{p, residual, grads_bf16, out_bf16, step, f, unc_residual, unc_bf16, flat_out_bf16,
+                                comm, stream});
+}
+
+int psgd_aggregate_mixed_ipc(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,
+                             psgd_flat* f, void* const* unc_bf16, void* const* unc_residual, void* flat_out_bf16,
+                             void* stream) {
+    return run(kMixedIpc, Call{p, residual, grads_bf16, out_bf16, step, f, unc_residual, unc_bf16, flat_out_bf16,
+                               nullptr, stream});
+}
+
+int psgd_aggregate_mixed_wide(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,
+                              psgd_flat* f, void* const* unc_bf16, void* const* unc_residual, void* flat_out_bf16,
+                              void* stream) {
+    return run(kMixedWide, Call{p, residual, grads_bf16, out_bf16, step, f, unc_residual, unc_bf16, flat_out_bf16,
+                                nullptr, stream});
+}
+
+int psgd_aggregate_mixed_wide_comm(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16,
+                                   int64_t step, psgd_flat* f, void* const* unc_bf16, void* const* unc_residual,
+                                   void* flat_out_bf16, psgd_comm* comm, void* stream) {
+    return run(kMixedWideComm, Call{p, residual, grads_bf16, out_bf16, step, f, unc_residual, unc_bf16,
+                                    flat_out_bf16, comm, stream});
+}
+
+int psgd_aggregate_mixed_comm_dst(psgd_plan* p, void* const* residual, void* const* dst_bf16, int64_t step,
+                                  psgd_flat* f, void* const* unc_residual, void* const* unc_dst_bf16, psgd_comm* comm,
+                                  void* stream) {
+    return run(kMixedCommDst, Call{p, residual, dst_bf16, nullptr, step, f, unc_residual, unc_dst_bf16, nullptr,
+                                   comm, stream});
+}
+
+int psgd_aggregate_mixed_ipc_dst(psgd_plan* p, void* const* residual, void* const* dst_bf16, int64_t step, psgd_flat* f,
+                                 void* const* unc_residual, void* const* unc_dst_bf16, void* stream) {
+    return run(kMixedIpcDst, Call{p, residual, dst_bf16, nullptr, step, f, unc_residual, unc_dst_bf16, nullptr,
+                                  nullptr, stream});
+}
+
+int psgd_aggregate_comm_dst(psgd_plan* p, void* const* grads, void* const* dst, int64_t step, psgd_flat* f,
+                            void* const* unc, void* const* unc_dst, psgd_comm* comm, void* stream) {
+    return run(kCommDst, Call{p, grads, dst, nullptr, step, f, unc, unc_dst, nullptr, comm, stream});
+}
+
+int psgd_aggregate_ipc_dst(psgd_plan* p, void* const* grads, void* const* dst, int64_t step, psgd_flat* f,
+                           void* const* unc, void* const* unc_dst, void* stream) {
+    return run(kIpcDst, Call{p, grads, dst, nullptr, step, f, unc, unc_dst, nullptr, nullptr, stream});
+}
+
+}  // extern "C"

@@ -46,8 +46,7 @@ psgd_plan::~psgd_plan() {
         (void)hipEventDestroy(e.second);
     }
     ipc_release(this);
-    mixed_release(this);
-    direct_release(this);
+    side_release(this);
     norm_release(this);
     guard_release(this);
     if (xerr_host) (void)hipHostFree(xerr_host);

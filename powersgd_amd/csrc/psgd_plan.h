@@ -3,14 +3,14 @@
 //   psgd_plan.cpp      plan lifecycle: create, queries, bind, buckets, timing
 //   psgd_step.cpp      step drivers (one stage function per IterRoute pass), the final-pass launch
 //                      functions shared with admission, and the reducer building blocks
-//   psgd_mixed.cpp     psgd_aggregate_mixed[_comm]: admission of the mixed instances, fold queries
-//   psgd_direct.cpp    psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst: admission, state, entry points
+//   psgd_onecall.cpp   the one-call steps that store their averages through an OutSink (psgd_aggregate_mixed*,
+//                      psgd_aggregate_comm_dst / _ipc_dst): admission, side state, entry points, queries
 //   psgd_norm.cpp      psgd_clip_outputs / psgd_plan_norm_form: form choice, state, launches
 //   psgd_guard.cpp     psgd_guard_outputs: skipping a non-finite step (state, launches)
 //   psgd_ipc.cpp       the IPC exchange arena and psgd_aggregate_ipc
 //   psgd_flat.cpp      flat pack and DDP run tables
 //   psgd_comm.cpp      the communicator behind psgd_aggregate_comm
-// Here: the plan, the per-call StepCtx, and the step route (IterRoute / OutRoute, psgd_plan::route /
+// Here: the plan, the output sink (OutSink), the per-call StepCtx, and the step route (IterRoute / OutRoute, psgd_plan::route /
 // out_route at the end of this file): the one place that decides what an iteration launches.
 // No torch: plain pointers, hipStream_t as void*. Never included by device code.
 #pragma once
@@ -206,6 +206,52 @@ namespace psgd {
 struct StepCtx;
 struct IterRoute;
 struct OutRoute;
+
+// Side state of the one-call steps (psgd_onecall.cpp), owned by the plan, nothing of it in the
+// caller's workspace: a pair of device pointer tables of `cap` entries in one allocation (`a`: the
+// bf16 sources, `b`: the destinations; DDP rebuilds its buckets once, so the pointers change after
+// the first iteration and are stable from then on) and an fp32 stage. Both grow on demand.
+struct SideTables {
+    TableCache a, b;
+    char* dev = nullptr;
+    size_t cap = 0;  // entries per table
+    float* stage = nullptr;
+    size_t stage_cap = 0;  // floats
+    // tables of `cnt` entries: bind, grow or re-bind; launches on `s` may still read the old ones
+    int room(size_t cnt, hipStream_t s) {
+        if (dev && cnt <= cap && a.n == cnt) return PSGD_OK;
+        if (dev) PSGD_HIP(hipStreamSynchronize(s));
+        if (!dev || cnt > cap) {
+            release_tables();
+            PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&dev), 2 * TableCache::bytes(cnt)));
+            cap = cnt;
+        }
+        a.bind(dev, cnt);
+        b.bind(dev + TableCache::bytes(cnt), cnt);
+        return PSGD_OK;
+    }
+    int stage_room(size_t floats, hipStream_t s) {
+        if (floats <= stage_cap) return PSGD_OK;
+        PSGD_HIP(hipStreamSynchronize(s));
+        if (stage) PSGD_HIP(hipFree(stage));
+        stage = nullptr;
+        stage_cap = 0;
+        PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&stage), floats * sizeof(float)));
+        stage_cap = floats;
+        return PSGD_OK;
+    }
+    void release_tables() {
+        a.release();
+        b.release();
+        if (dev) (void)hipFree(dev);
+        dev = nullptr;
+        cap = 0;
+    }
+    ~SideTables() {
+        release_tables();
+        if (stage) (void)hipFree(stage);
+    }
+};
 }  // namespace psgd
 
 using namespace psgd;  // the opaque C types below are global (include/psgd.h)
@@ -366,65 +412,36 @@ struct psgd_plan {
     bool xerr_set() const { return xerr_host && __atomic_load_n(xerr_host, __ATOMIC_ACQUIRE) != 0; }
     unsigned long long* stamp_buf = nullptr;  // diagnostic k_even stamps (PSGD_EVEN_STAMPS)
     size_t stamp_words = 0;
-    // psgd_aggregate_mixed (psgd_mixed.cpp): state of its own, created by the first mixed call or
-    // fold query of a bound plan; nothing of it lives in the caller's workspace (whose carve stays
-    // as it is), the device side is one small allocation owned by the plan
-    struct Mixed {
-        // admission of the mixed instances for the plan's current tiling (`key`): at least two
-        // waves per SIMD and no scratch, asked of the runtime like the fused final pass's
+    // The one-call steps (psgd_onecall.cpp). Admission of the instances an OutSink's final pass would
+    // launch on the plan's current tiling (at least two waves per SIMD, no scratch; asked of the
+    // runtime through the launch functions the drivers use), per sink kind, communicator kind and
+    // step parity. `key`: the plan fields a re-tiling can change; a cell is asked once per key.
+    struct Admission {
+        enum Kind { Bf16Dense, Bf16Tables, F32Tables, Bf16Ingest /* world size 1, the single-pass final kernel */, kKinds };
+        enum Comm { NoComm /* aggregate_ctx */, Many /* world size > 1 */, One /* a 1-rank communicator */, kComms };
         uint64_t key = ~uint64_t(0);
-        bool fin_in = false;       // single-pass k_final_odd_mix with the ingest fold
-        bool out[2] = {};          // the final pass of even / odd steps stores bf16
-        char* dev = nullptr;       // pointer tables of the bf16 gradients (TableCache slots)
-        size_t unc_cap = 0;        // ... and of the uncompressed bf16 gradients (entries)
-        char* unc_dev = nullptr;
-        TableCache src_tab, unc_tab;
-        psgd_runs* add = nullptr;  // the run-table ADD (k_runs_mix) of steps without an ingest fold
+        bool asked[kKinds][kComms] = {};
+        bool ok[kKinds][kComms][2] = {};
+    };
+    Admission adm;
+    // Their side state, made by the first call on a bound plan: `per` the tables of the plan's
+    // tensors, `unc` those of the flat plan's with the fp32 stage of the flat tail, and (mixed) the
+    // run-table ADD of the bf16 gradients (k_runs_mix) with its workspace. The bf16 entries and the
+    // fp32 destination-table entries keep an instance each: psgd_clip_dst reads `direct`'s stage and
+    // must not be satisfied by a stage a mixed call made.
+    struct Side {
+        SideTables per, unc;
+        psgd_runs* add = nullptr;
         char* add_ws = nullptr;
-        // psgd_aggregate_mixed_comm: admission of the final pass's bf16-output instance per
-        // communicator kind ([0]: world size > 1, [1]: a 1-rank communicator) and step parity, and
-        // the fp32 staging of the flat tail around its collective (made or grown by the first
-        // call that needs it, like unc_dev)
-        uint64_t comm_key = ~uint64_t(0);
-        bool comm_out[2][2] = {};
-        float* stage = nullptr;
-        size_t stage_cap = 0;      // floats
-        // psgd_aggregate_mixed_comm_dst: admission of the destination-table instances (a key of
-        // their own, indexed like comm_out), and the destinations' pointer tables, beside src_tab
-        // in `dev` and beside unc_tab in `unc_dev` (DDP rebuilds its buckets once: the pointers
-        // change after the first iteration and are stable from then on)
-        uint64_t dst_key = ~uint64_t(0);
-        bool dst_out[2][2] = {};
-        TableCache dst, unc_dst;
-        // psgd_aggregate_mixed_wide[_comm] (wide plans): admission of k_wide_apply_mix<rbucket>
-        // ([0]: two term sets, [1]: shared), asked once (its tiles never change)
-        bool wide_asked = false;
-        bool wide_ok[2] = {};
     };
-    Mixed* mixed = nullptr;
-    // psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst (psgd_direct.cpp): state of its own like
-    // Mixed, created by the first call or psgd_plan_dst_ok query; nothing of it lives in the
-    // caller's workspace. Admission of the fp32 destination-table instances of the output pass
-    // per communicator kind ([0]: world size > 1, [1]: one rank) and step parity under a key of
-    // its own; the destinations' pointer tables (change-detected: DDP rebuilds its buckets once);
-    // the fp32 staging of the flat tail (`flat->total` floats, grown by the first call that needs it)
-    struct Direct {
-        uint64_t key = ~uint64_t(0);
-        bool ok[2][2] = {};
-        char* dev = nullptr;
-        TableCache dst, unc_dst;
-        size_t unc_cap = 0;
-        char* unc_dev = nullptr;
-        float* stage = nullptr;
-        size_t stage_cap = 0;  // floats
-    };
-    Direct* direct = nullptr;
+    Side* mixed = nullptr;
+    Side* direct = nullptr;
     // psgd_clip_outputs (psgd_norm.cpp). The record: the term set the output pass of `step` read at
     // world size `world` (ApplyArgs::apx and alpha), written where that set is built
     // (decompress_impl; final_stage on steps whose fused final pass wrote the output) and
     // dropped when the next step's first iteration starts, so the norm entry never re-derives a
-    // route. Bucket calls (a span) leave none. `norm`: device state of its own like Mixed and
-    // Direct (work items, Gram partials, per-tensor squares, stream partials), made by the first
+    // route. Bucket calls (a span) leave none. `norm`: device state of its own like Side
+    // (work items, Gram partials, per-tensor squares, stream partials), made by the first
     // psgd_clip_outputs call; nothing of it lives in the caller's workspace.
     struct NormRec {
         bool have = false;
@@ -546,6 +563,43 @@ struct psgd_runs {
 
 namespace psgd {
 
+// Where a one-call step's averages go, and what feeds it. Built once per call on the entry
+// point's stack; the launch sites build the kernels' own MixArgs / DirectDst from it.
+//   element type  `bf16`: the fp32 codec runs on an fp32 error-feedback residual and stores bf16
+//                 averages (the mixed instances); else the plan's own dtype
+//   form          dense slabs at the plan's / the flat plan's offsets (`out`, `flat_out`), or
+//                 `tables`: per-tensor destinations (`dst` in the plan's tensor order, `unc_dst` in
+//                 the flat plan's; device pointer tables) with no slab
+//   stage         plan-owned fp32 buffer in the flat plan's layout: what a collective sums the flat
+//                 tail in when `flat_out` is not an fp32 slab
+//   src, unc_src  bf16 gradients added into the residual inside the step (device pointer tables):
+//                 `src` by the ingest fold of psgd_aggregate_mixed, `unc_src` by the flat ingest
+// A null sink in a context is the plain one: the plan's dtype into StepCtx::out / `out`.
+struct OutSink {
+    bool bf16 = false, tables = false;
+    void* out = nullptr;
+    void* flat_out = nullptr;
+    void* const* dst = nullptr;
+    void* const* unc_dst = nullptr;
+    float* stage = nullptr;
+    void* const* src = nullptr;
+    void* const* unc_src = nullptr;
+    // the flat tail's bf16 gradients are added in the step, (x + float(g)) / W in a launch of its
+    // own ahead of every collective; else the tail is packed as psgd_aggregate_comm packs it
+    bool ingests() const { return bf16 && !tables; }
+    // the fp32 buffer a collective (or the last fp32 exchange) sums the flat tail in
+    float* sums() const { return bf16 || tables ? stage : static_cast<float*>(flat_out); }
+    // FlatArgs::flat of the step's flat items: where the pack writes (sums()); with an ingest, which
+    // writes `stage` through MixArgs, the bf16 slab its round items store to
+    void* items_flat() const { return ingests() ? flat_out : sums(); }
+    // the final launch carries the flat tail's last hop as leading workgroups: copy items
+    // (unc_dst = stage, fp32 tables) or round items (bf16, where the route's instance has them:
+    // OutRoute::rounds)
+    bool copies() const { return tables && !bf16; }
+    MixArgs mix() const { return MixArgs{src, unc_src, stage}; }
+    DirectDst direct() const { return DirectDst{dst, unc_dst, stage}; }
+};
+
 // What one call of a step driver passes down to compress_impl / decompress_impl: built on the
 // entry point's stack, never stored in the plan.
 struct StepCtx {
@@ -561,30 +615,23 @@ struct StepCtx {
     // psgd_aggregate_ipc, ranks 2/4, two iterations: the exchange of iteration 0 left the summed
     // Q panels' Gram partials, so iteration 1 orthonormalises with k_orth_chain
     bool xgram = false;
-    // psgd_aggregate_mixed: the final pass (and the flat items riding in it) runs its mixed
-    // instance with these arguments; mix_in: the single-pass final kernel also ingests (ingest fold)
-    const MixArgs* mix = nullptr;
+    // where the step's averages go when not to `out` as the plan's dtype: the final pass (and the
+    // flat items riding in it) runs the sink's instance. mix_in: the single-pass final kernel of
+    // psgd_aggregate_mixed also ingests sink->src (ingest fold)
+    const OutSink* sink = nullptr;
     bool mix_in = false;
-    // psgd_aggregate_mixed_comm_dst: the mixed output pass stores at these per-tensor destinations
-    // (its destination-table instances) instead of `out`
-    const MixDst* dst = nullptr;
-    // psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst: the plan's own fp32 output pass stores at
-    // these per-tensor destinations (psgd_apply_dst.hip) instead of `out`, and c.fl's items are
-    // copy items from the staged flat tail
-    const DirectDst* fdst = nullptr;
 };
 
-// The contexts of the two one-call steps, shared by the drivers and by admission (psgd_mixed.cpp):
-// aggregate_ctx runs its iterations and output pass under world1_ctx(c); aggregate_comm_ctx its
-// output pass under comm_out_ctx(mix) (its iterations under a plain StepCtx with the flat fold)
+// The contexts of the one-call steps, shared by the drivers and by admission: aggregate_ctx runs
+// its iterations and output pass under world1_ctx(c); aggregate_comm_ctx / aggregate_ipc_ctx their
+// output pass under out_ctx(sink) (their iterations under a context without a sink)
 inline StepCtx world1_ctx(StepCtx c) {
     c.fuse = c.write_out = true;
     return c;
 }
-inline StepCtx comm_out_ctx(const MixArgs* mix, const MixDst* dst = nullptr) {
+inline StepCtx out_ctx(const OutSink* sink) {
     StepCtx c;
-    c.mix = mix;
-    c.dst = dst;
+    c.sink = sink;
     return c;
 }
 
@@ -610,7 +657,7 @@ inline int check_flat(const psgd_flat* f, bool args, bool type_ok, int type_code
 // ------------------------------------------------------------------ step route ------
 // What iteration `it` of `step` launches under a caller's StepCtx (fp32 / bf16 plans up to rank
 // 32; fp64 and wide plans have no fused forms and one fixed sequence). Plain data from plan flags
-// and the context: compress_impl launches what it says, admission (psgd_mixed.cpp) asks the
+// and the context: compress_impl launches what it says, admission (psgd_onecall.cpp) asks the
 // runtime about the instances it names, the plan queries report it.
 struct IterRoute {
     bool even;
@@ -639,19 +686,21 @@ struct OutRoute {
     int32_t out_nt;   // output stores nt only (world size 1, large plans)
     bool timed;       // benchmark timing covers this launch
     bool flat;        // the context's flat items ride in the launch (k_lowrank_out takes none)
-    bool dst;         // Mix / MixW / the mixed Lowrank: the destination-table instance (MixDst)
-    bool fdst;        // Plain: the fp32 destination-table instance (DirectDst)
+    bool tables;      // the destination-table instance of `inst` (OutSink::tables)
+    bool rounds;      // a bf16 sink at world size W: the instance carries the flat tail's round items
+                      // (the world-size-1 apply instance and k_wide_apply_mix take none: the round
+                      // follows as a launch of its own)
     int reduced_slot; // history slot of the earlier iterations' reduced factors (1: never copied to 2)
 };
 
 // psgd_step.cpp: the final pass of a route, for launching (the drivers) and for asking (admission:
 // ntiles = 0, empty arguments, `*waves` receives the resident waves per SIMD of the instance that
-// would run, 0 with scratch; only the fused and the mixed instances answer). `mix` null: the
+// would run, 0 with scratch; only the fused instances and a sink's answer). `sink` null: the
 // gradient type's own instance. launch_out_pass stamps the route's out_nt into `a`.
-hipError_t launch_final_pass(const psgd_plan* p, const IterRoute& r, const FinalArgs& a, const MixArgs* mix, int ntiles,
+hipError_t launch_final_pass(const psgd_plan* p, const IterRoute& r, const FinalArgs& a, const OutSink* sink, int ntiles,
                              hipStream_t s, int* waves);
-hipError_t launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArgs& a, const MixArgs* mix, int ntiles,
-                           hipStream_t s, int* waves, const MixDst* dst = nullptr, const DirectDst* fdst = nullptr);
+hipError_t launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArgs& a, const OutSink* sink, int ntiles,
+                           hipStream_t s, int* waves);
 
 // psgd_step.cpp
 int refresh_pointers(psgd_plan* p, void* const* grads, hipStream_t stream);
@@ -665,18 +714,9 @@ void ipc_release(psgd_plan* p);
 // psgd_ipc.cpp: what a step over the exchange needs of the session, checked before anything is
 // launched: open, no timed-out wait pending, a 32-bit epoch
 int ipc_check(const psgd_plan* p, int64_t step);
-// psgd_ipc.cpp: the world-size-W step of psgd_aggregate_ipc; with `mix`, of psgd_aggregate_mixed_ipc
-// (`grads` the fp32 residual, `out` / `flat_out` bf16, `unc` the uncompressed tensors' fp32
-// residual); with `mix` and `dst`, of psgd_aggregate_mixed_ipc_dst (`out` and `flat_out` unused);
-// with `fdst` alone, of psgd_aggregate_ipc_dst (`out` and `flat_out` unused: fdst->stage)
-int aggregate_ipc_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
-                      void* flat_out, hipStream_t s, const MixArgs* mix, const MixDst* dst,
-                      const DirectDst* fdst = nullptr);
-// psgd_mixed.cpp: frees the plan's mixed state
-void mixed_release(psgd_plan* p);
-// psgd_direct.cpp: frees the plan's direct-store state
-void direct_release(psgd_plan* p);
-// psgd_direct.cpp, for psgd_clip_dst (psgd_norm.cpp): the plan is one the direct-store calls serve
+// psgd_onecall.cpp: frees the plan's side state (psgd_plan::mixed / direct)
+void side_release(psgd_plan* p);
+// psgd_onecall.cpp, for psgd_clip_dst (psgd_norm.cpp): the plan is one the direct-store calls serve
 // by shape (fp32, not wide, one bucket); and the device tables of `dst` / `unc_dst` (the slots the
 // preceding direct-store call selected: no upload then) with the staged flat tail. A flat plan
 // whose tail the plan has not staged (no preceding direct-store call with at least f->total
@@ -689,20 +729,30 @@ void norm_release(psgd_plan* p);
 void guard_release(psgd_plan* p);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
 int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
-// psgd_step.cpp: the world-size-W step of psgd_aggregate_comm; with `mix`, of psgd_aggregate_mixed_comm;
-// with `mix` and `dst`, of psgd_aggregate_mixed_comm_dst (`out` and `flat_out` unused); with `fdst`
-// alone, of psgd_aggregate_comm_dst (`out` and `flat_out` unused: fdst->stage)
-int aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
-                       void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix, const MixDst* dst = nullptr,
-                       const DirectDst* fdst = nullptr);
+// The world-size-W step into `sink`: over a communicator (psgd_step.cpp; `comm` null: world size 1,
+// no collectives) or the plan's IPC exchange session (psgd_ipc.cpp). `grads` the fp32 / bf16 tensors
+// the codec runs on (a bf16 sink: the fp32 residual), `unc` the flat plan's (`f` null: no flat tail).
+// After the ADD where the entry has one; the same kernels, collectives and exchanges for every sink,
+// but for the flat tail's path and the final pass's instance.
+int aggregate_comm_ctx(psgd_plan* p, void* const* grads, int64_t step, psgd_flat* f, void* const* unc, psgd_comm* comm,
+                       hipStream_t s, const OutSink& sink);
+int aggregate_ipc_ctx(psgd_plan* p, void* const* grads, int64_t step, psgd_flat* f, void* const* unc, hipStream_t s,
+                      const OutSink& sink);
 
-// psgd_step.cpp: the step of psgd_aggregate_mixed_wide (`comm` null: world size 1) and
-// psgd_aggregate_mixed_wide_comm on a wide fp32 plan, after the ADD: `grads` the fp32 residual,
-// `out` / `flat_out` bf16, `unc` the uncompressed tensors' fp32 residual. The flat tail goes through
-// mix->stage (launch_flat_ingest first, launch_flat_round last), the iterations are compress_wide's
-// (with psgd_aggregate_comm's collectives), the final pass is launch_wide_apply_mix
-int aggregate_wide_mix_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f, void* const* unc,
-                           void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs& mix);
+// "refuse a poisoned communicator; poison on a failure that was not a refusal": `step(&refused)`
+// runs past the argument checks; a refusal (nothing launched, no collective issued) leaves the
+// communicator usable, any other failure can leave this rank's collective sequence short of its
+// peers', so the communicator refuses every later call (psgd_comm.cpp, comm_poison)
+template <typename Step>
+int with_comm(psgd_comm* comm, Step step) {
+    std::string why;
+    if (comm_poisoned(comm, &why))
+        return fail(PSGD_ERR_STATE, ("communicator unusable after an earlier failure: " + why).c_str());
+    bool refused = false;
+    const int st = step(&refused);
+    if (st && !refused) comm_poison(comm, psgd_last_error());
+    return st;
+}
 
 }  // namespace psgd
 
@@ -745,13 +795,14 @@ inline OutRoute psgd_plan::out_route(int64_t step, int world, const StepCtx& c) 
     // after a fused last iteration the residual is written: output only, or (psgd_aggregate at
     // world size 1, which wrote the output too) nothing
     o.kind = !fused_final(step, c.write_out) ? OutRoute::Apply : c.write_out ? OutRoute::None : OutRoute::Lowrank;
-    o.inst = !c.mix ? OutRoute::Plain : o.kind == OutRoute::Apply && world > 1 ? OutRoute::MixW : OutRoute::Mix;
+    const bool bf16 = c.sink && c.sink->bf16;
+    o.inst = !bf16 ? OutRoute::Plain : o.kind == OutRoute::Apply && world > 1 ? OutRoute::MixW : OutRoute::Mix;
     o.shared = world == 1;
     o.out_nt = world == 1 ? out_nt : 0;
     o.timed = o.kind == OutRoute::Apply;
-    o.fdst = c.mix == nullptr && c.fdst != nullptr;
-    o.flat = o.kind == OutRoute::Apply || c.mix != nullptr || o.fdst;
-    o.dst = c.mix != nullptr && c.dst != nullptr;
+    o.tables = c.sink && c.sink->tables;
+    o.flat = o.kind == OutRoute::Apply || bf16 || o.tables;
+    o.rounds = bf16 && !wide() && (o.kind == OutRoute::Lowrank || o.inst == OutRoute::MixW);
     // fused (world size 1): the reduced factor was never copied to history slot 2
     o.reduced_slot = fused_norm(c.fuse, 1) ? 1 : 2;
     return o;

@@ -219,10 +219,9 @@ int compress_wide(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hi
     return PSGD_OK;
 }
 
-// `mix` (psgd_aggregate_mixed_wide[_comm]): `grads` the fp32 residual, `out` bf16: the same arguments
-// to k_wide_apply_mix
-int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s,
-                    bool mix = false) {
+// `mix` (a bf16 sink: psgd_aggregate_mixed_wide[_comm]): `grads` the fp32 residual, `out` bf16: the
+// same arguments to k_wide_apply_mix
+int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s, bool mix) {
     if (int st = refresh_pointers(p, grads, s)) return st;
     const int I = p->iters;
     WideArgs a{};
@@ -419,7 +418,7 @@ int final_stage(const Iter& i) {
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     if (int st = timing_begin(p, i.s, &ev, true)) return st;  // benchmark timing: the final pass
     TimedScope ts(ev);
-    PSGD_HIP(launch_final_pass(p, i.r, fa, c.mix, fa.ntiles, i.s, nullptr));
+    PSGD_HIP(launch_final_pass(p, i.r, fa, c.sink, fa.ntiles, i.s, nullptr));
     return PSGD_OK;
 }
 
@@ -517,38 +516,39 @@ int product_stage(const Iter& i) {
 }
 }  // namespace
 
-hipError_t psgd::launch_final_pass(const psgd_plan* p, const IterRoute& r, const FinalArgs& a, const MixArgs* mix,
+hipError_t psgd::launch_final_pass(const psgd_plan* p, const IterRoute& r, const FinalArgs& a, const OutSink* sink,
                                    int ntiles, hipStream_t s, int* waves) {
     const int smax = fin_bucket(p->fin_smax);
     if (smax == 0) return hipErrorInvalidValue;  // no instance serves rows of that many segments
-    if (mix)  // psgd_aggregate_mixed: bf16 output, and the ingest fold of the single-pass form
-        return launch_final_mix(p->rbucket, r.final_nres, smax, r.ingest, a, *mix, ntiles, s, waves);
+    if (sink && sink->bf16)  // psgd_aggregate_mixed: bf16 output, and the ingest fold of the single-pass form
+        return launch_final_mix(p->rbucket, r.final_nres, smax, r.ingest, a, sink->mix(), ntiles, s, waves);
     return launch_final_odd(p->dtype, p->rbucket, r.final_nres, smax, a, ntiles, s, waves);
 }
 
-hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArgs& a, const MixArgs* mix, int ntiles,
-                                 hipStream_t s, int* waves, const MixDst* dst, const DirectDst* fdst) {
+hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArgs& a, const OutSink* sink, int ntiles,
+                                 hipStream_t s, int* waves) {
     a.out_nt = o.out_nt;
     const int R = p->rbucket, I = p->iters;
-    if (o.fdst) {  // psgd_aggregate_comm_dst: the fp32 averages go to the per-tensor destinations
-        if (p->dtype != PSGD_F32) return hipErrorInvalidValue;
-        a.odst = fdst->dst;
-        if (o.kind == OutRoute::Lowrank) return launch_lowrank_dst(R, I, a, *fdst, ntiles, s, waves);
-        return launch_apply_dst(R, I, o.shared, a, *fdst, ntiles, s, waves);
+    if (o.inst == OutRoute::Plain) {
+        if (!o.tables)
+            return o.kind == OutRoute::Lowrank ? launch_lowrank_out(p->dtype, R, I, a, ntiles, s)
+                                               : launch_apply(p->dtype, R, I, o.shared, a, ntiles, s);
+        if (p->dtype != PSGD_F32) return hipErrorInvalidValue;  // fp32 averages at the per-tensor destinations
+        a.odst = sink->dst;
+        const DirectDst t = sink->direct();
+        return o.kind == OutRoute::Lowrank ? launch_lowrank_dst(R, I, a, t, ntiles, s, waves)
+                                           : launch_apply_dst(R, I, o.shared, a, t, ntiles, s, waves);
     }
-    if (o.dst) {  // psgd_aggregate_mixed_comm_dst: the averages go to the per-tensor destinations
-        a.odst = dst->dst;
-        if (o.kind == OutRoute::Lowrank) return launch_lowrank_mix_dst(R, I, a, *mix, dst->unc_dst, ntiles, s, waves);
-        if (o.inst == OutRoute::MixW) return launch_apply_mix_w_dst(R, I, a, *mix, dst->unc_dst, ntiles, s, waves);
+    const MixArgs x = sink->mix();
+    if (o.tables) {  // bf16 averages at the per-tensor destinations
+        a.odst = sink->dst;
+        if (o.kind == OutRoute::Lowrank) return launch_lowrank_mix_dst(R, I, a, x, sink->unc_dst, ntiles, s, waves);
+        if (o.inst == OutRoute::MixW) return launch_apply_mix_w_dst(R, I, a, x, sink->unc_dst, ntiles, s, waves);
         return launch_apply_mix_dst(R, I, a, ntiles, s, waves);
     }
-    if (o.kind == OutRoute::Lowrank)
-        return mix ? launch_lowrank_mix(R, I, a, *mix, ntiles, s, waves) : launch_lowrank_out(p->dtype, R, I, a, ntiles, s);
-    switch (o.inst) {
-        case OutRoute::Mix: return launch_apply_mix(R, I, a, *mix, ntiles, s, waves);
-        case OutRoute::MixW: return launch_apply_mix_w(R, I, a, *mix, ntiles, s, waves);
-        default: return launch_apply(p->dtype, R, I, o.shared, a, ntiles, s);
-    }
+    if (o.kind == OutRoute::Lowrank) return launch_lowrank_mix(R, I, a, x, ntiles, s, waves);
+    return o.inst == OutRoute::MixW ? launch_apply_mix_w(R, I, a, x, ntiles, s, waves)
+                                    : launch_apply_mix(R, I, a, x, ntiles, s, waves);
 }
 
 int psgd::compress_impl(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hipStream_t s, StepCtx c) {
@@ -577,7 +577,7 @@ int psgd::aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStrea
 int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s,
                           StepCtx c) {
     if (p->f64()) return decompress_f64(p, grads, out, step, world, s);
-    if (p->wide()) return decompress_wide(p, grads, out, step, world, s);
+    if (p->wide()) return decompress_wide(p, grads, out, step, world, s, c.sink && c.sink->bf16);
     const OutRoute o = p->out_route(step, world, c);
     if (o.kind == OutRoute::None) return PSGD_OK;  // output written by the fused last iteration
     if (int st = refresh_pointers(p, grads, s)) return st;
@@ -596,7 +596,7 @@ int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t s
     aa.nterms = I;
     aa.alpha = float(1.0 / double(world));  // reference alpha = 1 / num_workers (:218)
     aa.ntiles = nt;
-    if (c.fl && o.flat) aa.flat = *c.fl;  // uncompressed tensors (mixed_comm: their round items) ride in the launch
+    if (c.fl && o.flat) aa.flat = *c.fl;  // uncompressed tensors (a sink's: their round or copy items) ride in the launch
     if (nt + aa.flat.nitems == 0) return PSGD_OK;
     // for psgd_clip_outputs: the term set this pass reads (world size 1: the shared instance reads the
     // local terms alone, history slots 0 / 1, and never the state buffer)
@@ -605,7 +605,7 @@ int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t s
     if (o.timed)
         if (int st = timing_begin(p, s, &ev, true)) return st;
     TimedScope ts(ev);
-    PSGD_HIP(launch_out_pass(p, o, aa, c.mix, nt, s, nullptr, c.dst, c.fdst));
+    PSGD_HIP(launch_out_pass(p, o, aa, c.sink, nt, s, nullptr));
     return PSGD_OK;
 }
 
@@ -646,81 +646,41 @@ int refresh_table(psgd_plan* p, void* const* ptrs, TableCache& tab, hipStream_t 
 
 }  // namespace
 
-// `mix` (psgd_aggregate_mixed_comm): `grads` the fp32 residual, `out` / `flat_out` bf16, `unc` the
-// uncompressed tensors' fp32 residual; the flat tail is staged in mix->stage (fp32) around its
-// collective: ingest-pack in a launch of its own first, the round items in the final launch.
-// `mix` and `dst` (psgd_aggregate_mixed_comm_dst): `grads` already holds residual + gradients, so
-// nothing is ingested: the flat tail is packed as psgd_aggregate_comm packs it (x / W, x = +0.0,
-// flat_pack_item<float>), with mix->stage as its flat buffer, and the round items store into
-// dst->unc_dst.
-// `fdst` alone (psgd_aggregate_comm_dst): psgd_aggregate_comm's own sequence with fdst->stage where
-// `flat_out` goes (packed by the same kernels: inside the first even product's launch, else
-// flat_pack_item<float> in a launch of its own), the final pass's fp32 destination-table instance,
-// and copy items (fdst->unc_dst = stage) as its leading workgroups
-int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f,
-                             void* const* unc, void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs* mix,
-                             const MixDst* dst, const DirectDst* fdst) {
+// The flat tail by the sink's properties. An ingesting sink: stage = (x + float(g)) / W, x = g = +0.0
+// in a launch of its own first. Every other: x / W, x = +0.0 into the sink's fp32 sum buffer (utils.py:
+// 43-47, powersgd.py:29-30), inside the first even product's launch when the step starts even, else a
+// launch of its own. The last collective sums that buffer; then a plain sink is done, a copying
+// sink's items (unc_dst = stage) lead the final launch, and a bf16 sink's round items (flat_out or
+// unc_dst = bf16(stage)) lead it where the instance carries them, else follow as a launch of their own
+int psgd::aggregate_comm_ctx(psgd_plan* p, void* const* grads, int64_t step, psgd_flat* f, void* const* unc,
+                             psgd_comm* comm, hipStream_t s, const OutSink& sink) {
     const bool has_flat = f != nullptr;
-    const int world = comm_world(comm);
-    // x / W into the flat buffer, x = 0 (utils.py:43-47, powersgd.py:29-30): inside the first
-    // even product's launch when the step starts even, else its own launch
+    const int world = comm ? comm_world(comm) : 1;
+    const MixArgs x = sink.mix();
     FlatArgs fa{};
-    const bool ingest = mix && !dst;
-    const bool fold = has_flat && !ingest && p->even(step, 0) && !p->wide();  // wide products carry no flat pack
-    if (fdst) flat_out = fdst->stage;  // the collective's fp32 buffer; copy items follow it
-    if (fold || ((mix || fdst) && has_flat)) {
-        if (int st = flat_args(f, unc, dst ? static_cast<void*>(mix->stage) : flat_out, world, s, &fa)) return st;
-        if (ingest) PSGD_HIP(launch_flat_ingest(fa, *mix, s));
+    const bool fold = has_flat && !sink.ingests() && p->even(step, 0) && !p->wide();  // wide products carry no flat pack
+    if (has_flat) {
+        if (int st = flat_args(f, unc, sink.items_flat(), world, s, &fa)) return st;
+        if (sink.ingests()) PSGD_HIP(launch_flat_ingest(fa, x, s));
         else if (!fold) PSGD_HIP(launch_flat_pack(f->dtype, fa, s));
-    } else if (has_flat) {
-        if (int st = psgd_flat_pack(f, unc, flat_out, world, s)) return st;
     }
-    float* const tail = mix ? mix->stage : static_cast<float*>(flat_out);
     StepCtx c;
     c.fl = fold ? &fa : nullptr;
     for (int it = 0; it < p->iters; ++it) {
         if (int st = compress_impl(p, grads, step, it, s, c)) return st;
-        const bool e = p->even(step, it);
-        const bool last = it == p->iters - 1;
-        if (int st = comm_allreduce(comm, e ? p->Q : p->P, size_t(e ? p->qtot : p->ptot),
-                                    last && has_flat ? tail : nullptr, last && has_flat ? size_t(f->total) : 0, s))
-            return st;
-    }
-    StepCtx d = comm_out_ctx(mix, dst);
-    if (fdst) {  // the copy items ride in the final launch, whichever it is
-        d.fdst = fdst;
-        d.fl = has_flat ? &fa : nullptr;
-    }
-    if (!mix) return decompress_impl(p, grads, out, step, world, s, d);
-    // the round items ride in every final launch built for them; a 1-rank communicator's unfused
-    // final pass is the world-size-1 instance, whose flat items ingest: the round follows it
-    const OutRoute o = p->out_route(step, world, d);
-    const bool ride = o.kind == OutRoute::Lowrank || o.inst == OutRoute::MixW;
-    d.fl = has_flat && ride ? &fa : nullptr;
-    if (int st = decompress_impl(p, grads, out, step, world, s, d)) return st;
-    if (has_flat && !ride) PSGD_HIP(dst ? launch_flat_round_dst(fa, *mix, dst->unc_dst, s) : launch_flat_round(fa, *mix, s));
-    return PSGD_OK;
-}
-
-int psgd::aggregate_wide_mix_ctx(psgd_plan* p, void* const* grads, void* out, int64_t step, psgd_flat* f,
-                                 void* const* unc, void* flat_out, psgd_comm* comm, hipStream_t s, const MixArgs& mix) {
-    const int world = comm ? comm_world(comm) : 1;
-    FlatArgs fa{};
-    if (f) {  // stage = (x + float(g)) / W, x = g = +0.0: ahead of every collective
-        if (int st = flat_args(f, unc, flat_out, world, s, &fa)) return st;
-        PSGD_HIP(launch_flat_ingest(fa, mix, s));
-    }
-    for (int it = 0; it < p->iters; ++it) {
-        if (int st = compress_impl(p, grads, step, it, s, StepCtx{})) return st;
         if (!comm) continue;
         const bool e = p->even(step, it);
         const bool last = it == p->iters - 1;
-        if (int st = comm_allreduce(comm, e ? p->Q : p->P, size_t(e ? p->qtot : p->ptot), last && f ? mix.stage : nullptr,
-                                    last && f ? size_t(f->total) : 0, s))
+        if (int st = comm_allreduce(comm, e ? p->Q : p->P, size_t(e ? p->qtot : p->ptot),
+                                    last && has_flat ? sink.sums() : nullptr, last && has_flat ? size_t(f->total) : 0, s))
             return st;
     }
-    if (int st = decompress_wide(p, grads, out, step, world, s, true)) return st;
-    if (f) PSGD_HIP(launch_flat_round(fa, mix, s));
+    StepCtx d = out_ctx(&sink);
+    const bool rounds = p->out_route(step, world, d).rounds;
+    d.fl = has_flat && (sink.copies() || rounds) ? &fa : nullptr;
+    if (int st = decompress_impl(p, grads, sink.out, step, world, s, d)) return st;
+    if (has_flat && sink.bf16 && !rounds)
+        PSGD_HIP(sink.tables ? launch_flat_round_dst(fa, x, sink.unc_dst, s) : launch_flat_round(fa, x, s));
     return PSGD_OK;
 }
 
@@ -813,16 +773,13 @@ int psgd_aggregate_comm(psgd_plan* p, void* const* grads, void* out, int64_t ste
             return st;
     // a poisoned communicator is refused before the step launches anything: the caller's
     // gradients and the P/Q state stay as they were
-    std::string why;
-    if (comm_poisoned(comm, &why))
-        return fail(PSGD_ERR_STATE, ("communicator unusable after an earlier failure: " + why).c_str());
-    DevScope scope(p->device);
-    const int st = aggregate_comm_ctx(p, grads, out, step, has_flat ? f : nullptr, unc, flat_out, comm,
-                                      static_cast<hipStream_t>(stream), nullptr);
-    // a failure past the argument checks can leave this rank's collective sequence short of its
-    // peers': the communicator refuses every later call (psgd_comm.cpp, comm_poison)
-    if (st) comm_poison(comm, psgd_last_error());
-    return st;
+    return with_comm(comm, [&](bool*) {
+        DevScope scope(p->device);
+        OutSink sink;
+        sink.out = out;
+        sink.flat_out = flat_out;
+        return aggregate_comm_ctx(p, grads, step, has_flat ? f : nullptr, unc, comm, static_cast<hipStream_t>(stream), sink);
+    });
 }
 
 // ------------------------------------------------- building blocks (reducer variants) ---

@@ -19,14 +19,15 @@ struct Caller {
 };
 
 std::string step_launches(psgd_plan& p, const Caller& who, int64_t step) {
-    const MixArgs none{};
+    OutSink bf16;
+    bf16.bf16 = true;
     StepCtx c;
     if (who.ipc) {
         c.fuse = p.rbucket == 1;
         c.raw_slot = 2;
         c.xgram = p.qfold_ok && p.iters == 2 && p.even(step, 0);
     }
-    if (who.mix && who.world1) c.mix = &none;
+    if (who.mix && who.world1) c.sink = &bf16;
     if (who.world1) c = world1_ctx(c);
     std::string s;
     for (int it = 0; it < p.iters; ++it) {
@@ -38,11 +39,11 @@ std::string step_launches(psgd_plan& p, const Caller& who, int64_t step) {
             case IterRoute::PassOdd: s += "odd reduce"; break;
             case IterRoute::PassOddEven: s += "final_oe"; break;
             case IterRoute::PassFromOddEven: s += "reduce"; break;
-            case IterRoute::PassFinal: s += std::string(r.proj ? "final_proj" : "final_odd") + (c.mix ? "_mix" : ""); break;
+            case IterRoute::PassFinal: s += std::string(r.proj ? "final_proj" : "final_odd") + (c.sink ? "_mix" : ""); break;
         }
         s += "; ";
     }
-    const OutRoute o = p.out_route(step, who.world1 ? 1 : 2, who.world1 ? c : comm_out_ctx(who.mix ? &none : nullptr));
+    const OutRoute o = p.out_route(step, who.world1 ? 1 : 2, who.world1 ? c : out_ctx(who.mix ? &bf16 : nullptr));
     if (o.kind == OutRoute::None) return s + "=> (none)";
     s += o.kind == OutRoute::Lowrank ? "=> lowrank" : "=> apply";
     return s + (o.inst == OutRoute::Plain ? (o.kind == OutRoute::Lowrank ? "_out" : "") : o.inst == OutRoute::Mix ? "_mix" : "_mix_w");

@@ -637,6 +637,75 @@ int psgd_aggregate_ipc_dst(psgd_plan* plan, void* const* grads, void* const* dst
                            psgd_flat* flat, void* const* unc, void* const* unc_dst, void* stream);
 int psgd_plan_dst_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
 
+/* ------------- the fused SGD step: the final pass applies the update to the weights ------------ */
+/* One tensor's hyperparameters, fp32 (converted from doubles once on the host; `cd` = 1 - dampening
+ * computed in double, then rounded). `first`: this tensor's momentum buffer has not been written
+ * yet (torch's momentum_buffer = None): buf' = d.
+ * THE UPDATE of element e with the step's average g (torch.optim.SGD's single-tensor rule; every
+ * multiply and add rounded to fp32 on its own, never contracted into an fma):
+ *   d    = weight_decay != 0 ? g + weight_decay * p        : g
+ *   buf' = momentum == 0 ? (buf is neither read nor written) : first ? d : momentum * buf + cd * d
+ *   u    = momentum == 0 ? d : nesterov ? d + momentum * buf' : buf'
+ *   p'   = p + (-lr) * u
+ * maximize is not served. */
+typedef struct psgd_sgd_hyper {
+    float lr, momentum, cd, weight_decay;
+    int32_t nesterov, first;
+} psgd_sgd_hyper;
+
+/* psgd_sgd_update: THE UPDATE, element-wise, in one launch (k_sgd_update) over `count` tensors given
+ * as host arrays of device pointers: g[i] the averages (read only), p[i] the weights, buf[i] the
+ * momentum buffers (`buf` NULL, or an entry NULL: allowed where hyper[i].momentum == 0), numel[i]
+ * dense fp32 elements each, hyper[i] the tensor's record. Each of the three pointers is 4-byte
+ * aligned or better, independently: a work item (at most 4096 elements of one tensor, 64-bit
+ * offsets) whose three addresses agree modulo 16 bytes runs as a head of 0-3 elements, 16-byte
+ * vectors and a tail, any other as 4-byte accesses; every load is issued before the first store and
+ * every access goes through a descriptor of the item's own elements. Nothing outside the numel
+ * elements of p[i] / buf[i] is written. Also the second half of a destination or slab step: call it
+ * on the averages psgd_aggregate_comm_dst / psgd_aggregate* left, on the same stream.
+ * `plan`: a bound plan keeps the tables (work items, pointers, hyperparameters) in device memory of
+ * its own, change-detected and uploaded on `stream` from pinned memory; the host never
+ * waits for the stream. NULL: nothing is kept; the tables are uploaded and the launch awaited.
+ * Refusals, in this order, all before any launch: a null g / p / numel / hyper or count < 1:
+ * PSGD_ERR_VALUE; a plan that is not bound: PSGD_ERR_STATE; a null g[i] / p[i], a null buf[i] where
+ * momentum != 0, numel[i] < 0: PSGD_ERR_VALUE; a pointer that is not 4-byte aligned: PSGD_ERR_LAYOUT. */
+int psgd_sgd_update(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* buf,
+                    const int64_t* numel, const psgd_sgd_hyper* hyper, void* stream);
+
+/* psgd_aggregate_comm_sgd: the world-size-W step whose final pass, at the element where it would
+ * have stored an average, applies THE UPDATE to the weight and the momentum buffer instead: the
+ * n x m averages never exist in memory and no optimizer pass follows. DEFINED as this sequence and
+ * equal to it bit for bit (every p, buf, residual, P/Q state; the same collectives in order and count):
+ *   1. psgd_aggregate_comm_dst(plan, grads, dst, step, flat, unc, unc_dst, comm) into scratch
+ *      destinations
+ *   2. psgd_sgd_update on those averages with params / bufs (then unc_params / unc_bufs) and hyper
+ * `params`, `bufs` are in the plan's tensor order, `unc_params`, `unc_bufs` in the flat plan's;
+ * `hyper` holds the plan's tensors' records, then the flat plan's (num_tensors + flat count). `bufs`
+ * / `unc_bufs` (or an entry) may be NULL where the tensor's momentum is 0. `comm` NULL: world size
+ * 1, no collectives (the communicator sequence's kernels all the same).
+ * Where it runs: the final pass of step 1 (k_apply with two term sets, its shared form for one
+ * rank, k_lowrank_out after a fused k_final_odd; VALU tiles at rank buckets 1-8, matrix-core tiles
+ * at 16 / 32) as its update instance (psgd_sgd_dst.hip): tiles, loads, LDS staging, the MFMA
+ * sequence, alpha x the accumulators and the residual store are the destination instance's, so g
+ * has the same bits; where that stored a vector of averages this loads the vector of p (and buf)
+ * ahead of the tile's arithmetic, applies THE UPDATE and stores p' (and buf'): 16 bytes where the
+ * tile's first element is 16-byte aligned in p and in buf, else four 4-byte accesses, chosen once
+ * per tile, through descriptors that span the tile's rows of that tensor alone. The stores of p'
+ * and buf' are plain (read again by the next forward pass / the next step), whatever the plan's
+ * output cache policy. The hyperparameter records are read once per tile, wave-uniformly. The flat
+ * tail is staged and summed as in step 1; the leading workgroups of the final launch apply THE
+ * UPDATE to unc_params / unc_bufs from the stage.
+ * Eligible: psgd_plan_dst_ok's rule with the update instances in the destination instances' place.
+ * psgd_plan_sgd_ok: *ok = 1 for such a plan (`momentum_used` is validated only: one instance
+ * serves both, the momentum branch is wave-uniform).
+ * Refusals: psgd_aggregate_comm_dst's codes in its order (a null params / hyper: "null argument";
+ * a p or buf that is not 4-byte aligned: PSGD_ERR_LAYOUT; a null buf where momentum != 0:
+ * PSGD_ERR_VALUE), all before any launch or collective. */
+int psgd_aggregate_comm_sgd(psgd_plan* plan, void* const* grads, void* const* params, void* const* bufs,
+                            const psgd_sgd_hyper* hyper, int64_t step, psgd_flat* flat, void* const* unc,
+                            void* const* unc_params, void* const* unc_bufs, psgd_comm* comm, void* stream);
+int psgd_plan_sgd_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t momentum_used, int32_t* ok);
+
 /* ------------------------ global-norm clipping of a step's averages (clip_grad_norm_) ---------- */
 /* torch.nn.utils.clip_grad_norm_ (L2) over everything a step returned, on the stream, with no host
  * synchronisation: norm = sqrt(sum of squares of the compressed averages `out` and of the dense

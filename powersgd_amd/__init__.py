@@ -13,7 +13,8 @@ from powersgd_amd.powersgd import Aggregator, AllReduce, Config, PowerSGD  # noq
 from powersgd_amd.residual import Fp32ResidualPowerSGD  # noqa: F401
 from powersgd_amd.utils import params_in_optimizer
 
-__all__ = ["Aggregator", "AllReduce", "Config", "Fp32ResidualPowerSGD", "PowerSGD", "optimizer_step"]
+__all__ = ["Aggregator", "AllReduce", "Config", "Fp32ResidualPowerSGD", "PowerSGD", "optimizer_step", "sgd_step",
+           "sgd_step_applies"]
 
 
 def optimizer_step(optimizer: torch.optim.Optimizer, aggregator: Aggregator):
@@ -34,3 +35,6 @@ def optimizer_step(optimizer: torch.optim.Optimizer, aggregator: Aggregator):
     optimizer.step()
     for p, g in zip(params, grads):
         p.grad = g
+
+
+from powersgd_amd.sgd import sgd_step, sgd_step_applies  # noqa: E402,F401  (uses optimizer_step above)

@@ -100,6 +100,9 @@ _SIGNATURES = {
     "psgd_clip_dst": ([_vp, _i64, _i32, _vp, _vp, _vp, _dbl, _vp, _vp], _i32),
     "psgd_plan_clip_dst_ok": ([_vp, _P_i32], _i32),
     "psgd_guard_outputs": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _i32),
+    "psgd_sgd_update": ([_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_aggregate_comm_sgd": ([_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_sgd_ok": ([_vp, _i64, _i32, _i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -109,6 +112,27 @@ class _IpcInfo(ctypes.Structure):  # psgd_ipc_info (include/psgd.h)
     _fields_ = [("arena_allocs", _i64), ("arena_opens", _i64), ("arena_reuses", _i64), ("arena_frees", _i64),
                 ("own_va", ctypes.c_uint64), ("peer_va", ctypes.c_uint64), ("own_nonce", ctypes.c_uint32),
                 ("peer_nonce_seen", ctypes.c_uint32)]
+
+class SgdHyper(ctypes.Structure):  # psgd_sgd_hyper (include/psgd.h)
+    _fields_ = [("lr", ctypes.c_float), ("momentum", ctypes.c_float), ("cd", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("nesterov", _i32), ("first", _i32)]
+
+
+def sgd_hyper(records):
+    """A psgd_sgd_hyper array from (lr, momentum, dampening, weight_decay, nesterov, first) tuples of
+    Python numbers: each rounded to fp32 once, here; ``cd = 1 - dampening`` in double, then rounded."""
+    return (SgdHyper * max(1, len(records)))(*[SgdHyper(lr, mu, 1.0 - damp, wd, int(bool(nest)), int(bool(first)))
+                                                for lr, mu, damp, wd, nest, first in records])
+
+
+def sgd_update(plan: Optional["Plan"], g, p, buf, numel: Sequence[int], hyper, stream: int) -> None:
+    """psgd_sgd_update: the element-wise SGD update over ``len(numel)`` tensors. ``g`` / ``p`` / ``buf``:
+    addresses of host arrays of device pointers (``buf`` None: no tensor has momentum); ``hyper``
+    from ``sgd_hyper``. ``plan`` (bound) keeps the tables on the device; None: uploaded and awaited."""
+    n = len(numel)
+    check(lib().psgd_sgd_update(plan._h if plan is not None else None, n, g, p, buf, (_i64 * max(1, n))(*numel),
+                                ctypes.addressof(hyper), stream))
+
 
 _lib = None
 
@@ -325,6 +349,24 @@ class Plan:
         anything is launched or any collective issued."""
         check(lib().psgd_aggregate_comm_dst(self._h, grads, dst, step, flat._h if flat is not None else None, unc,
                                             unc_dst, comm._h if comm is not None else None, stream))
+
+    # --- the fused SGD step: the final pass applies the update to the weights
+    def sgd_ok(self, step: int, world: int, momentum_used: bool = True) -> int:
+        """1 where ``aggregate_comm_sgd`` serves this plan (psgd_plan_sgd_ok: ``dst_ok``'s rule with the
+        update instances), 0 for a plan it refuses."""
+        ok = _i32()
+        check(lib().psgd_plan_sgd_ok(self._h, step, world, int(bool(momentum_used)), ctypes.byref(ok)))
+        return int(ok.value)
+
+    def aggregate_comm_sgd(self, grads, params, bufs, hyper, step: int, comm: Optional["Comm"], stream: int, flat=None,
+                           unc=None, unc_params=None, unc_bufs=None) -> None:
+        """psgd_aggregate_comm_sgd: ``aggregate_comm_dst`` followed by ``sgd_update`` in one call; the final
+        pass applies the update to ``params[i]`` / ``bufs[i]`` (then the flat plan's) and stores no
+        average. ``hyper``: ``sgd_hyper`` records, the plan's tensors then the flat plan's. ``comm`` None:
+        world size 1, no collectives."""
+        check(lib().psgd_aggregate_comm_sgd(self._h, grads, params, bufs, ctypes.addressof(hyper) if hyper is not None
+                                            else None, step, flat._h if flat is not None else None, unc, unc_params,
+                                            unc_bufs, comm._h if comm is not None else None, stream))
 
     def aggregate_ipc_dst(self, grads, dst, step: int, stream: int, flat=None, unc=None, unc_dst=None) -> None:
         """psgd_aggregate_ipc_dst: the same over the plan's open exchange session (``aggregate_ipc``)."""

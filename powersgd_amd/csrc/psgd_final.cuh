@@ -654,8 +654,11 @@ constexpr int kLowrankUR = PSGD_LOWRANK_UR;
 // DST (psgd_aggregate_mixed_comm_dst, T = bf16_pin_t; kDstVec / kDstElem): the output goes to
 // a.odst[d.tensor], a tensor of any 2-byte alignment; the store form as in apply_tile (psgd_stream.cuh).
 // T = float (psgd_aggregate_comm_dst): a tensor of any 4-byte alignment, st_vec_dstf's forms
+// kDstSgdVec / kDstSgdElem (psgd_aggregate_comm_sgd, T = float): the update forms, as in apply_tile
 template <typename T, int R, int NI, int V, int DST = 0>
-__device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t) {
+__device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t,
+                                             const SgdTile* sg = nullptr) {
+    constexpr bool SGD = DST >= kDstSgdVec;
     const TileGeom g = tile_geom<V>(d, t);
     const int r = d.r;
     T* obase;
@@ -663,6 +666,8 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
     else obase = static_cast<T*>(a.out) + d.out_off;
     const rsrc_t rO = make_rsrc(obase + g.row_begin * g.m,
                                 uint32_t((g.row_end - g.row_begin) * g.m * int64_t(sizeof(T))));
+    rsrc_t rB = rO;
+    if constexpr (SGD) rB = sgd_buf_rsrc(*sg, g.row_begin * g.m, uint32_t((g.row_end - g.row_begin) * g.m * 4));
     const int nt = NI > 0 ? NI : a.nterms;
     constexpr int NC = NI > 0 ? NI : 1;
     float ba[NC][V][R];
@@ -692,13 +697,20 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
                 float o[V];
 #pragma unroll
                 for (int v = 0; v < V; ++v) o[v] = 0.f;
+                float pv[V], bv[V];  // the update forms: p and buf ahead of the row's term chain
+                if constexpr (SGD) {
+                    const uint32_t so = uint32_t(((row < g.row_end ? row : row0) - g.row_begin) * g.m + g.col0) * 4u;
+                    sgd_ld<DST>(rO, so, pv);
+                    sgd_ld<DST>(rB, so, bv);
+                }
 #pragma unroll
                 for (int k = 0; k < NI; ++k)
 #pragma unroll
                     for (int v = 0; v < V; ++v) o[v] = o[v] + alpha * dotr<R>(pa[u][k], ba[k][v]);
                 if (g.active && row < g.row_end) {
                     const uint32_t off = uint32_t((row - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(T));
-                    if constexpr (DST != 0 && std::is_same<T, float>::value) st_vec_dstf<DST>(rO, off, o);
+                    if constexpr (SGD) sgd_apply<DST, V>(*sg, rO, rB, off, o, pv, bv);
+                    else if constexpr (DST != 0 && std::is_same<T, float>::value) st_vec_dstf<DST>(rO, off, o);
                     else if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
                     else st_vec<T>(rO, off, o);
                 }
@@ -711,6 +723,12 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
         float o[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) o[v] = 0.f;
+        float pv[V], bv[V];
+        if constexpr (SGD) {
+            const uint32_t so = uint32_t((row - g.row_begin) * g.m + g.col0) * 4u;
+            sgd_ld<DST>(rO, so, pv);
+            sgd_ld<DST>(rB, so, bv);
+        }
         for (int k = 0; k < nt; ++k) {
             float aa[R];
             ld_factor<R>(gconst<float>(a.apx.p[k]) + d.poff + prow, r, aa);
@@ -728,7 +746,8 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
         }
         if (g.active) {
             const uint32_t off = uint32_t((row - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(T));
-            if constexpr (DST != 0 && std::is_same<T, float>::value) st_vec_dstf<DST>(rO, off, o);
+            if constexpr (SGD) sgd_apply<DST, V>(*sg, rO, rB, off, o, pv, bv);
+            else if constexpr (DST != 0 && std::is_same<T, float>::value) st_vec_dstf<DST>(rO, off, o);
             else if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
             else st_vec<T>(rO, off, o);
         }

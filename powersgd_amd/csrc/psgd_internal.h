@@ -6,7 +6,7 @@
 #include <string>
 #include <stdint.h>
 
-struct psgd_comm;  // include/psgd.h (psgd_comm.cpp)
+#include "psgd.h"  // psgd_sgd_hyper: the per-tensor record the update kernels read
 
 namespace psgd {
 
@@ -550,6 +550,42 @@ hipError_t launch_apply_dst(int R, int nterms, bool shared, const ApplyArgs& a, 
                             hipStream_t s, int* waves);
 hipError_t launch_lowrank_dst(int R, int nterms, const ApplyArgs& a, const DirectDst& t, int ntiles, hipStream_t s,
                               int* waves);
+
+// psgd_aggregate_comm_sgd: the destination-table final pass with the SGD update (include/psgd.h,
+// THE UPDATE) applied where the average would have been stored. The parameter table is read as
+// ApplyArgs::odst; the rest is this second kernel argument: the momentum buffers (`bufs`, the
+// plan's tensor order; an entry is read only where its record's momentum != 0), the flat plan's
+// parameters and buffers, the staged flat tail, and the records: hyper[i] of the plan's tensor i,
+// hyper[unc0 + k] of the flat plan's tensor k.
+struct SgdDst {
+    void* const* bufs;
+    void* const* unc_p;
+    void* const* unc_buf;
+    const float* stage;
+    const psgd_sgd_hyper* hyper;
+    int32_t unc0;
+};
+// psgd_sgd_dst.hip: the update instances of launch_apply_dst / launch_lowrank_dst (the same NI and
+// SHARED; a.flat's items are update items on unc_p / unc_buf from `stage` and come first; `waves`
+// as above), and the element-wise k_sgd_update the fused form is defined against: one launch over
+// work items of at most kRunItem elements of one tensor.
+hipError_t launch_apply_sgd(int R, int nterms, bool shared, const ApplyArgs& a, const SgdDst& x, int ntiles,
+                            hipStream_t s, int* waves);
+hipError_t launch_lowrank_sgd(int R, int nterms, const ApplyArgs& a, const SgdDst& x, int ntiles, hipStream_t s,
+                              int* waves);
+struct SgdItem {
+    int64_t off;          // first element in the tensor
+    int32_t tensor, cnt;  // tensor index, elements (<= kRunItem)
+};
+struct SgdArgs {
+    const SgdItem* items;
+    void* const* g;    // per tensor: the averages, the weights, the momentum buffers
+    void* const* p;
+    void* const* buf;
+    const psgd_sgd_hyper* hyper;
+    int32_t nitems;
+};
+hipError_t launch_sgd_update(const SgdArgs& a, hipStream_t s);
 
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),

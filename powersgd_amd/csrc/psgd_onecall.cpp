@@ -14,6 +14,9 @@
 //   fp32 tables  psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst, the default DDP hook's completion:
 //                psgd_aggregate_comm (psgd_aggregate_ipc) on the gradients with every fp32 average
 //                stored at the tensor's own destination, so no slab is written and no gather runs.
+//   fp32 update  psgd_aggregate_comm_sgd: psgd_aggregate_comm_dst into scratch destinations, then
+//                psgd_sgd_update on them; the final pass applies the SGD update to the weights and the
+//                momentum buffers at the element where it would have stored the average.
 // Every entry is a descriptor (Entry) and its arguments (Call): one preamble runs the checks in the
 // entry's documented order, one body makes the side state, asks admission (a refusal launches
 // nothing), builds the sink and hands it to the step driver of the entry's transport.
@@ -29,7 +32,9 @@ struct Entry {
     const char* name;  // for messages
     enum Via { World1, Comm, Xchg } via;
     bool wide, tables, bf16;
-    Adm::Kind kind() const { return !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense; }
+    bool sgd = false;  // the update sink: `peer` the parameters, Call::bufs / hyper beside them; a null
+                       // communicator is world size 1 without collectives
+    Adm::Kind kind() const { return sgd ? Adm::F32Sgd : !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense; }
 };
 
 // The arguments by role. `state`: the fp32 tensors the codec runs on (a bf16 sink: the residual; else
@@ -47,16 +52,28 @@ struct Call {
     void* flat_out;
     psgd_comm* comm;
     void* stream;
+    // the update sink: momentum buffers (a table or an entry may be null where momentum == 0) and
+    // the records, the plan's tensors first
+    void* const* bufs = nullptr;
+    void* const* unc_bufs = nullptr;
+    const psgd_sgd_hyper* hyper = nullptr;
 };
 
 // The plans an entry serves, by shape. bf16 sinks: fp32, one bucket, rank buckets 1 / 2 / 4 (VALU
 // tiles) and 16 / 32 (matrix-core tiles, psgd_mixed_mfma.hip), not 8 (the VALU tile whose
 // register-cached two-set instances sit at the scratch edge); the wide entries: what those refuse by
 // rank. fp32 tables: fp32, one bucket, not wide
-const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code) {
+const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool sgd = false) {
     *code = PSGD_ERR_VALUE;
     const int rb = p->rbucket;
-    if (!bf16) {
+    if (sgd) {
+        if (p->dtype != PSGD_F32) {
+            *code = PSGD_ERR_DTYPE;
+            return "psgd_aggregate_comm_sgd takes an fp32 plan";
+        }
+        if (p->wide()) return "psgd_aggregate_comm_sgd serves rank buckets 1 to 32";
+        if (p->spans.size() > 1) return "psgd_aggregate_comm_sgd takes a plan of one bucket";
+    } else if (!bf16) {
         if (p->dtype != PSGD_F32) {
             *code = PSGD_ERR_DTYPE;
             return "psgd_aggregate_comm_dst / psgd_aggregate_ipc_dst take an fp32 plan";
@@ -86,8 +103,9 @@ const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code) {
 // plan's only sink instance is k_wide_apply_mix<rbucket> (shared terms at world size 1)
 bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
     OutSink sink;
-    sink.bf16 = kind != Adm::F32Tables;
-    sink.tables = kind == Adm::Bf16Tables || kind == Adm::F32Tables;
+    sink.sgd = kind == Adm::F32Sgd;
+    sink.bf16 = kind != Adm::F32Tables && !sink.sgd;
+    sink.tables = kind == Adm::Bf16Tables || kind == Adm::F32Tables || sink.sgd;
     const int world = comm == Adm::Many ? 2 : 1;
     int w = 0;
     hipError_t e = hipErrorInvalidValue;
@@ -133,6 +151,9 @@ bool admitted(psgd_plan* p, Adm::Kind kind, Adm::Comm comm) {
 // per communicator kind; the wide entries and the fp32 tables are eligible as a whole plan or not
 bool eligible(psgd_plan* p, const Entry& e, int world) {
     if (e.via == Entry::World1 && !e.wide) return admitted(p, e.kind(), Adm::NoComm);
+    // the update entry is defined as the destination-table step followed by psgd_sgd_update: it serves
+    // the plans whose destination instances are admitted too
+    if (e.sgd && !(admitted(p, Adm::F32Tables, Adm::Many) && admitted(p, Adm::F32Tables, Adm::One))) return false;
     if (e.wide || !e.bf16) return admitted(p, e.kind(), Adm::Many) && admitted(p, e.kind(), Adm::One);
     return admitted(p, e.kind(), world == 1 ? Adm::One : Adm::Many);
 }
@@ -194,7 +215,8 @@ void release(psgd_plan::Side*& slot) {
 // Leaves c.f null where there is no flat tail
 int preamble(const Entry& e, Call& c) {
     const psgd_plan* p = c.p;
-    const bool args = p && c.state && c.peer && (e.tables || c.out) && (e.via != Entry::Comm || c.comm);
+    const bool args = p && c.state && c.peer && (e.tables || c.out) && (e.via != Entry::Comm || c.comm || e.sgd) &&
+                      (!e.sgd || c.hyper);
     if (e.via == Entry::Xchg) {
         if (!args) return fail(PSGD_ERR_VALUE, "null argument");
         if (c.step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
@@ -205,7 +227,7 @@ int preamble(const Entry& e, Call& c) {
     if (!e.tables)
         if (int st = check_out(c.out)) return st;
     int code = PSGD_ERR_VALUE;
-    const char* why = ineligible(p, e.bf16, e.wide, &code);
+    const char* why = ineligible(p, e.bf16, e.wide, &code, e.sgd);
     if (why && !e.bf16) return fail(code, why);
     if (!c.f || c.f->total == 0) c.f = nullptr;
     if (const psgd_flat* f = c.f) {
@@ -224,7 +246,9 @@ int preamble(const Entry& e, Call& c) {
     // every tensor's two pointers: the bf16 side (gradients, or destinations like them) 2-byte
     // aligned and the fp32 residual 4-byte; fp32 destinations 4-byte
     const uintptr_t al = e.bf16 ? 2 : 4;
-    const char* al_msg = e.bf16 ? "bf16 gradients must be 2-byte aligned" : "fp32 destinations must be 4-byte aligned";
+    const char* al_msg = e.bf16  ? "bf16 gradients must be 2-byte aligned"
+                         : e.sgd ? "parameters must be 4-byte aligned"
+                                 : "fp32 destinations must be 4-byte aligned";
     for (size_t i = 0; i < p->shapes.size(); ++i) {
         if (!c.state[i] || !c.peer[i]) return fail(PSGD_ERR_VALUE, "null gradient pointer");
         if (reinterpret_cast<uintptr_t>(c.peer[i]) % al) return fail(PSGD_ERR_LAYOUT, al_msg);
@@ -234,6 +258,8 @@ int preamble(const Entry& e, Call& c) {
     if (c.f && !e.bf16)
         for (int32_t i = 0; i < c.f->count; ++i)
             if (reinterpret_cast<uintptr_t>(c.unc_peer[i]) % al) return fail(PSGD_ERR_LAYOUT, al_msg);
+    if (e.sgd)
+        if (int st = sgd_check(p, c.bufs, c.f, c.unc_bufs, c.hyper)) return st;
     if (e.via == Entry::Xchg) {
         if (int st = ipc_check(p, c.step)) return st;
         if (c.f && c.f->total > p->ipc_flat_cap)
@@ -249,6 +275,17 @@ int body(const Entry& e, const Call& c, bool* refused) {
     psgd_flat* f = c.f;
     hipStream_t s = static_cast<hipStream_t>(c.stream);
     DevScope scope(p->device);
+    if (e.sgd) {  // its tables are psgd_plan::Sgd's (psgd_sgd.cpp), and there is no transport but the communicator
+        if (int st = refresh_pointers(p, c.state, s)) return st;
+        if (!eligible(p, e, 1)) {
+            *refused = true;
+            return fail(PSGD_ERR_VALUE, std::string(e.name) + ": no admitted update instance of this plan's final pass "
+                                                              "(two waves per SIMD, no scratch)");
+        }
+        OutSink sink;
+        if (int st = sgd_select(p, c.peer, c.bufs, f, c.unc_peer, c.unc_bufs, c.hyper, s, &sink)) return st;
+        return aggregate_comm_ctx(p, c.state, c.step, f, c.unc_state, c.comm, s, sink);
+    }
     psgd_plan::Side*& slot = e.bf16 ? p->mixed : p->direct;
     if (int st = ensure(p, slot, e.bf16)) return st;
     psgd_plan::Side& m = *slot;
@@ -310,7 +347,7 @@ int body(const Entry& e, const Call& c, bool* refused) {
 
 int run(const Entry& e, Call c) {
     if (int st = preamble(e, c)) return st;
-    if (e.via == Entry::Comm) return with_comm(c.comm, [&](bool* refused) { return body(e, c, refused); });
+    if (e.via == Entry::Comm && c.comm) return with_comm(c.comm, [&](bool* refused) { return body(e, c, refused); });
     bool refused = false;
     return body(e, c, &refused);
 }
@@ -332,6 +369,7 @@ const Entry kMixedCommDst{"psgd_aggregate_mixed_comm_dst", Entry::Comm, false, t
 const Entry kMixedIpcDst{"psgd_aggregate_mixed_ipc_dst", Entry::Xchg, false, true, true};
 const Entry kCommDst{"psgd_aggregate_comm_dst", Entry::Comm, false, true, false};
 const Entry kIpcDst{"psgd_aggregate_ipc_dst", Entry::Xchg, false, true, false};
+const Entry kCommSgd{"psgd_aggregate_comm_sgd", Entry::Comm, false, true, false, true};
 
 }  // namespace
 
@@ -409,6 +447,25 @@ int psgd_plan_dst_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t
     int code = 0;
     if (ineligible(plan, false, false, &code)) return PSGD_OK;
     return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kCommDst, world) ? 1 : 0; });
+}
+
+int psgd_plan_sgd_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t momentum_used, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    if (momentum_used != 0 && momentum_used != 1) return fail(PSGD_ERR_VALUE, "momentum_used is 0 or 1");
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, false, false, &code, true)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kCommSgd, world) ? 1 : 0; });
+}
+
+int psgd_aggregate_comm_sgd(psgd_plan* p, void* const* grads, void* const* params, void* const* bufs,
+                            const psgd_sgd_hyper* hyper, int64_t step, psgd_flat* f, void* const* unc,
+                            void* const* unc_params, void* const* unc_bufs, psgd_comm* comm, void* stream) {
+    Call c{p, grads, params, nullptr, step, f, unc, unc_params, nullptr, comm, stream};
+    c.bufs = bufs;
+    c.unc_bufs = unc_bufs;
+    c.hyper = hyper;
+    return run(kCommSgd, c);
 }
 
 int psgd_aggregate_mixed_flat(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,

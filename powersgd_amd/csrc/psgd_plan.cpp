@@ -49,6 +49,7 @@ psgd_plan::~psgd_plan() {
     side_release(this);
     norm_release(this);
     guard_release(this);
+    sgd_release(this);
     if (xerr_host) (void)hipHostFree(xerr_host);
     if (stamp_buf) (void)hipFree(stamp_buf);
 }

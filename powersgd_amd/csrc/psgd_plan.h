@@ -417,7 +417,10 @@ struct psgd_plan {
     // runtime through the launch functions the drivers use), per sink kind, communicator kind and
     // step parity. `key`: the plan fields a re-tiling can change; a cell is asked once per key.
     struct Admission {
-        enum Kind { Bf16Dense, Bf16Tables, F32Tables, Bf16Ingest /* world size 1, the single-pass final kernel */, kKinds };
+        enum Kind {
+            Bf16Dense, Bf16Tables, F32Tables, Bf16Ingest /* world size 1, the single-pass final kernel */,
+            F32Sgd /* the update instances of psgd_aggregate_comm_sgd */, kKinds
+        };
         enum Comm { NoComm /* aggregate_ctx */, Many /* world size > 1 */, One /* a 1-rank communicator */, kComms };
         uint64_t key = ~uint64_t(0);
         bool asked[kKinds][kComms] = {};
@@ -466,6 +469,11 @@ struct psgd_plan {
     // gradient tensors' work items, the gradient pointer tables), made by the first call
     struct Guard;
     Guard* guard = nullptr;
+    // psgd_sgd_update / psgd_aggregate_comm_sgd (psgd_sgd.cpp): device state of its own like Guard
+    // (the change-detected tables of pointers, work items and hyperparameter records, the fp32
+    // stage of the flat tail), made by the first call
+    struct Sgd;
+    Sgd* sgd = nullptr;
     int64_t xslot_off(int64_t step, int it) const {  // byte offset of a slot in every buffer
         return kXchgHeader + ((step & 1) * iters + it) * ipc_slot * int64_t(sizeof(float));
     }
@@ -574,6 +582,10 @@ namespace psgd {
 //                 tail in when `flat_out` is not an fp32 slab
 //   src, unc_src  bf16 gradients added into the residual inside the step (device pointer tables):
 //                 `src` by the ingest fold of psgd_aggregate_mixed, `unc_src` by the flat ingest
+//   sgd           psgd_aggregate_comm_sgd: an fp32 `tables` sink whose destinations are the
+//                 parameters; the final pass applies the SGD update there instead of storing the
+//                 average, with the momentum buffers (`bufs`, `unc_bufs`) and the per-tensor records
+//                 (`hyper`: the plan's tensors, then the flat plan's from `hyper_unc0`)
 // A null sink in a context is the plain one: the plan's dtype into StepCtx::out / `out`.
 struct OutSink {
     bool bf16 = false, tables = false;
@@ -584,6 +596,12 @@ struct OutSink {
     float* stage = nullptr;
     void* const* src = nullptr;
     void* const* unc_src = nullptr;
+    bool sgd = false;
+    void* const* bufs = nullptr;
+    void* const* unc_bufs = nullptr;
+    const psgd_sgd_hyper* hyper = nullptr;
+    int32_t hyper_unc0 = 0;
+    SgdDst sgd_dst() const { return SgdDst{bufs, unc_dst, unc_bufs, stage, hyper, hyper_unc0}; }
     // the flat tail's bf16 gradients are added in the step, (x + float(g)) / W in a launch of its
     // own ahead of every collective; else the tail is packed as psgd_aggregate_comm packs it
     bool ingests() const { return bf16 && !tables; }
@@ -727,6 +745,15 @@ int direct_select(psgd_plan* p, void* const* dst, const psgd_flat* f, void* cons
 void norm_release(psgd_plan* p);
 // psgd_guard.cpp: frees the plan's guard state
 void guard_release(psgd_plan* p);
+// psgd_sgd.cpp: frees the plan's update state; and, for psgd_aggregate_comm_sgd (psgd_onecall.cpp),
+// the checks of the update's own arguments (after the plan's: null bufs where a record has momentum,
+// PSGD_ERR_VALUE; a buf that is not 4-byte aligned, PSGD_ERR_LAYOUT) and the sink's device tables
+// (params, bufs, the flat plan's, the records; the stage of `f->total` floats), change-detected and
+// uploaded on `s`
+void sgd_release(psgd_plan* p);
+int sgd_check(const psgd_plan* p, void* const* bufs, const psgd_flat* f, void* const* unc_bufs, const psgd_sgd_hyper* hyper);
+int sgd_select(psgd_plan* p, void* const* params, void* const* bufs, const psgd_flat* f, void* const* unc_params,
+               void* const* unc_bufs, const psgd_sgd_hyper* hyper, hipStream_t s, OutSink* sink);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
 int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
 // The world-size-W step into `sink`: over a communicator (psgd_step.cpp; `comm` null: world size 1,

@@ -535,6 +535,9 @@ hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArg
                                                : launch_apply(p->dtype, R, I, o.shared, a, ntiles, s);
         if (p->dtype != PSGD_F32) return hipErrorInvalidValue;  // fp32 averages at the per-tensor destinations
         a.odst = sink->dst;
+        if (sink->sgd)  // the update applied where the average would have been stored
+            return o.kind == OutRoute::Lowrank ? launch_lowrank_sgd(R, I, a, sink->sgd_dst(), ntiles, s, waves)
+                                               : launch_apply_sgd(R, I, o.shared, a, sink->sgd_dst(), ntiles, s, waves);
         const DirectDst t = sink->direct();
         return o.kind == OutRoute::Lowrank ? launch_lowrank_dst(R, I, a, t, ntiles, s, waves)
                                            : launch_apply_dst(R, I, o.shared, a, t, ntiles, s, waves);

@@ -240,6 +240,91 @@ __device__ __forceinline__ void st_vec_dstf(rsrc_t r, uint32_t off, const float 
     StIo<float>::template st1<AUX>(r, off, v[0]);
 }
 
+// The update forms (psgd_aggregate_comm_sgd, psgd_sgd_dst.hip; TO = float): at the element where the
+// destination instance stores an average the tile applies the SGD update (include/psgd.h, THE
+// UPDATE) to the weight and the momentum buffer. kDstSgdVec / kDstSgdElem as kDstVec / kDstElem:
+// 16-byte accesses where the tile's first element is 16-byte aligned in p and in buf, else four
+// 4-byte ones (the kernel picks per tile). a.odst is the parameter table; the tile's momentum
+// buffer and its tensor's record come in a SgdTile, built once per tile from workgroup-uniform
+// loads (the record lives in SGPRs, its branches are scalar).
+constexpr int kDstSgdVec = 3, kDstSgdElem = 4;
+struct SgdTile {
+    float* buf;  // the tensor's momentum buffer; null where momentum == 0
+    psgd_sgd_hyper h;
+};
+// a product that exists as a rounded fp32 value of its own: the empty asm consumes it, so no
+// following add can contract it into an fma (the fused and the element-wise form agree bit for bit)
+__device__ __forceinline__ float mul_rn(float a, float b) {
+    float t = a * b;
+    asm volatile("" : "+v"(t));
+    return t;
+}
+__device__ __forceinline__ void sgd_update(const psgd_sgd_hyper& h, float g, float& p, float& b) {
+    float d = g;
+    if (h.weight_decay != 0.f) d = g + mul_rn(h.weight_decay, p);
+    float u = d;
+    if (h.momentum != 0.f) {
+        b = h.first ? d : mul_rn(h.momentum, b) + mul_rn(h.cd, d);
+        u = h.nesterov ? d + mul_rn(h.momentum, b) : b;
+    }
+    p = p + mul_rn(-h.lr, u);
+}
+// a vector of p or buf at byte offset `off` of its descriptor (out of range: zeros, no access)
+template <int DST>
+__device__ __forceinline__ void sgd_ld(rsrc_t r, uint32_t off, float (&v)[4]) {
+    if constexpr (DST == kDstSgdElem) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            v[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off + 4u * uint32_t(e), 0, 0));
+    } else {
+        const auto x = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+        v[0] = __uint_as_float(x[0]); v[1] = __uint_as_float(x[1]);
+        v[2] = __uint_as_float(x[2]); v[3] = __uint_as_float(x[3]);
+    }
+}
+template <int DST>
+__device__ __forceinline__ void sgd_ld(rsrc_t r, uint32_t off, float (&v)[1]) {
+    v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
+}
+// plain stores (aux 0): p' is read by the next forward pass, buf' by the next step
+template <int DST>
+__device__ __forceinline__ void sgd_st(rsrc_t r, uint32_t off, const float (&v)[4]) {
+    if constexpr (DST == kDstSgdElem) StIo<float>::template st4e<0>(r, off, v);
+    else StIo<float>::template st4<0>(r, off, v);
+}
+template <int DST>
+__device__ __forceinline__ void sgd_st(rsrc_t r, uint32_t off, const float (&v)[1]) {
+    StIo<float>::template st1<0>(r, off, v[0]);
+}
+// The epilogue: the averages `o` pinned in the form the destination instance hands them to its
+// store (one 128-bit vector of their bits, or one dword: the same sink for the arithmetic upstream,
+// as bf16_pin_t), then the update on the already loaded p / buf and the two stores
+template <int DST, int V>
+__device__ __forceinline__ void sgd_apply(const SgdTile& sg, rsrc_t rP, rsrc_t rB, uint32_t off, const float (&o)[V],
+                                          float (&pv)[V], float (&bv)[V]) {
+    float g[V];
+    if constexpr (V == 4) {
+        typedef unsigned v4u __attribute__((ext_vector_type(4)));
+        v4u x = {__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])};
+        asm volatile("" : "+v"(x));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) g[e] = __uint_as_float(x[e]);
+    } else {
+        uint32_t x = __float_as_uint(o[0]);
+        asm volatile("" : "+v"(x));
+        g[0] = __uint_as_float(x);
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) sgd_update(sg.h, g[e], pv[e], bv[e]);
+    sgd_st<DST>(rP, off, pv);
+    if (sg.h.momentum != 0.f) sgd_st<DST>(rB, off, bv);
+}
+// the momentum buffer's descriptor over `bytes` from element `first`; empty (every load zero, no
+// access) where the tensor has none
+__device__ __forceinline__ rsrc_t sgd_buf_rsrc(const SgdTile& sg, int64_t first, uint32_t bytes) {
+    return make_rsrc(sg.buf ? sg.buf + first : nullptr, sg.buf ? bytes : 0u);
+}
+
 template <typename T>
 struct Io;
 
@@ -1223,7 +1308,14 @@ hipError_t dispatch_odd_mfma(int R, int nres, const ProductArgs& a, int ntiles, 
 // psgd_apply_dst.hip) the destination is 4-byte aligned or better and the forms are 16 bytes /
 // four 4-byte stores (st_vec_dstf, dst_al16).
 template <typename T, int R, int NI, bool SHARED, int V, bool ONT = false, typename TO = T, int DST = 0>
-__device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t) {
+__device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t,
+                                           const SgdTile* sg = nullptr) {
+    constexpr bool SGD = DST >= kDstSgdVec;  // the update forms: rO spans the tile's rows of p, rB of buf
+    // rows in flight per lane. The update forms of the two-set instances that cache 12 or more
+    // factor columns per set keep 2: their destination twins sit at the register edge with 4
+    // (k_apply_dst<4, 3, false>: 255 VGPRs), and p, buf and the update's temporaries do not fit
+    // beside them in two waves per SIMD. Rows are independent: no element's arithmetic changes
+    constexpr int UR = SGD && NI > 0 && !SHARED && R * NI >= 12 ? 2 : kUnroll;
     const TileGeom g = tile_geom<V>(d, t);
     const int r = d.r;
     const gptr<T> G = gmut<T>(a.grads[t.tensor]);
@@ -1234,6 +1326,8 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
     const uint32_t tb = uint32_t((g.row_end - g.row_begin) * g.m * int64_t(sizeof(T)));
     const rsrc_t rD = make_rsrc(Dp + g.row_begin * g.m, tb);
     const rsrc_t rO = make_rsrc(Op + g.row_begin * g.m, uint32_t((g.row_end - g.row_begin) * g.m * int64_t(sizeof(TO))));
+    rsrc_t rB = rO;
+    if constexpr (SGD) rB = sgd_buf_rsrc(*sg, g.row_begin * g.m, tb);
     const int nt = NI > 0 ? NI : a.nterms;
     constexpr int NC = NI > 0 ? NI : 1;
     constexpr int NA = (NI > 0 && !SHARED) ? NI : 1;
@@ -1252,18 +1346,18 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
     }
     const float alpha = a.alpha;
 
-    // batches of kUnroll rows: all gradient rows AND their error-feedback factor rows are
+    // batches of UR rows: all gradient rows AND their error-feedback factor rows are
     // loaded before the first is consumed (factor rows loaded inside the term loop were a
-    // chain of kUnroll dependent round trips per batch)
+    // chain of UR dependent round trips per batch)
     struct Batch {
-        float x[kUnroll][V];
-        int64_t rc[kUnroll];
-        float ap[NC][kUnroll][R];
-        float aa[NA][kUnroll][R];
+        float x[UR][V];
+        int64_t rc[UR];
+        float ap[NC][UR][R];
+        float aa[NA][UR][R];
     };
     auto load = [&](Batch& b, int64_t row) {
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
+        for (int u = 0; u < UR; ++u) {
             const int64_t rr = row + u * g.stride;
             b.rc[u] = rr < g.row_end ? rr : g.row_begin;
             Io<T>::ld(G + b.rc[u] * g.m + g.ccol, b.x[u]);
@@ -1272,7 +1366,7 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
 #pragma unroll
             for (int k = 0; k < NI; ++k)
 #pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
+                for (int u = 0; u < UR; ++u) {
                     const int32_t prow = int32_t(b.rc[u]) * r;
                     ld_factor<R>(gconst<float>(a.res.p[k]) + d.poff + prow, r, b.ap[k][u]);
                     if constexpr (!SHARED) ld_factor<R>(gconst<float>(a.apx.p[k]) + d.poff + prow, r, b.aa[k][u]);
@@ -1281,11 +1375,19 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
     };
     auto process = [&](Batch& b, int64_t row) {
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
+        for (int u = 0; u < UR; ++u) {
             const int32_t prow = int32_t(b.rc[u]) * r;
             float o[V];
 #pragma unroll
             for (int v = 0; v < V; ++v) o[v] = 0.f;
+            // the update forms: this row's p and buf go out ahead of its term chain (they do not
+            // depend on it); 32-bit offsets into the descriptors, no address is kept
+            float pv[V], bv[V];
+            if constexpr (SGD) {
+                const uint32_t so = uint32_t((b.rc[u] - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(float));
+                sgd_ld<DST>(rO, so, pv);
+                sgd_ld<DST>(rB, so, bv);
+            }
             for (int k = 0; k < nt; ++k) {
                 float ap[R], aa[R];
                 if constexpr (NI > 0) {
@@ -1326,7 +1428,9 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
             if (g.active && row + u * g.stride < g.row_end) {
                 const uint32_t eo = uint32_t((b.rc[u] - g.row_begin) * g.m + g.col0);
                 st_vec<T>(rD, eo * uint32_t(sizeof(T)), b.x[u]);
-                if constexpr (DST != 0 && std::is_same<TO, float>::value)
+                if constexpr (SGD)
+                    sgd_apply<DST, V>(*sg, rO, rB, eo * uint32_t(sizeof(float)), o, pv, bv);
+                else if constexpr (DST != 0 && std::is_same<TO, float>::value)
                     st_vec_dstf<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
                 else if constexpr (DST != 0)
                     st_vec_dst<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
@@ -1335,7 +1439,7 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
             }
         }
     };
-    for (int64_t row = g.first_row; row < g.row_end; row += kUnroll * g.stride) {
+    for (int64_t row = g.first_row; row < g.row_end; row += UR * g.stride) {
         Batch b;
         load(b, row);
         process(b, row);
@@ -1370,7 +1474,9 @@ struct ApplyMfmaLds {
 // they are rounded (bf16_pin_t). The loads, the staging, the MFMA sequence and the residual store
 // are the fp32 instance's.
 template <typename T, int R, bool SHARED, bool ONT, int DST = 0, typename TO = T>
-__device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDesc& d, const Tile& t, float* qs) {
+__device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDesc& d, const Tile& t, float* qs,
+                                                const SgdTile* sg = nullptr) {
+    constexpr bool SGD = DST >= kDstSgdVec;  // the update forms (T = TO = float): rO spans p, rB buf
     constexpr int KQ = R / 4;
     constexpr int RP = ApplyMfmaLds<R>::RP;
     constexpr int NS = SHARED ? 1 : 2;
@@ -1417,6 +1523,8 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
     const rsrc_t rG = make_rsrc(Gp + row_begin * m, tb);
     const rsrc_t rD = make_rsrc(Dp + row_begin * m, tb);
     const rsrc_t rO = make_rsrc(Op + row_begin * m, uint32_t((row_end - row_begin) * int64_t(m) * int64_t(sizeof(TO))));
+    rsrc_t rB = rO;
+    if constexpr (SGD) rB = sgd_buf_rsrc(*sg, row_begin * m, tb);
     const uint32_t cofs = active ? uint32_t(col) * s : kOob;
     const uint32_t rstride = uint32_t(m) * s;
     const bool pvec = r == R && (d.poff & 3) == 0;
@@ -1426,6 +1534,16 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
         float x[4][4];
 #pragma unroll
         for (int v = 0; v < 4; ++v) BufIo<T>::ld4(rG, (rb + v) * rstride + cofs, x[v]);
+        // the update forms: the block's p and buf quads go out with the gradient's, ahead of the
+        // staging reads and the MFMA chain; the offsets are formed again at the stores
+        float pv[SGD ? 4 : 1][4], bv[SGD ? 4 : 1][4];
+        if constexpr (SGD) {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                sgd_ld<DST>(rO, (rb + v) * rstride + cofs, pv[v]);
+                sgd_ld<DST>(rB, (rb + v) * rstride + cofs, bv[v]);
+            }
+        }
         const int64_t pi = b0 + ri < row_end ? b0 + ri : row_begin;  // A-operand row (clamped)
         f32x4_t tacc[NS][4];
 #pragma unroll
@@ -1489,6 +1607,8 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
                 const uint32_t oo_off = in ? ((rb + v) * uint32_t(m) + uint32_t(col)) * uint32_t(sizeof(TO)) : kOob;
                 if constexpr (DST != 0) st_vec_dst<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, oo_off, oo);
                 else st_vec<TO, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, oo_off, oo);
+            } else if constexpr (SGD) {
+                sgd_apply<DST, 4>(*sg, rO, rB, off, oo, pv[v], bv[v]);
             } else if constexpr (DST != 0) {
                 st_vec_dstf<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, oo);
             } else {

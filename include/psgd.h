@@ -706,6 +706,80 @@ int psgd_aggregate_comm_sgd(psgd_plan* plan, void* const* grads, void* const* pa
                             void* const* unc_params, void* const* unc_bufs, psgd_comm* comm, void* stream);
 int psgd_plan_sgd_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t momentum_used, int32_t* ok);
 
+/* ------- the fused Adam / AdamW step: the final pass updates the weights and both moments ------- */
+/* One tensor's record, fp32. Every scalar is computed in double on the host exactly as torch's
+ * _single_tensor_adam does for a non-capturable optimizer, then rounded once to fp32; t is the
+ * tensor's step count after the increment:
+ *   w1 = 1 - beta1, w2 = 1 - beta2, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t),
+ *   decay = 1 - lr * weight_decay; `decoupled`: AdamW's decay of the weight (else weight_decay * p
+ *   joins the gradient).
+ * THE UPDATE of element e with the step's average g (torch's single-tensor rule for amsgrad=False,
+ * maximize=False; every multiply, add, sqrt and divide rounded to fp32 on its own, never contracted;
+ * sqrt and divide correctly rounded):
+ *   d   = (!decoupled && weight_decay != 0) ? g + weight_decay * p : g
+ *   p0  = ( decoupled && weight_decay != 0) ? decay * p            : p
+ *   m'  = w1 < 0.5 ? m + w1 * (d - m) : d - (1 - w1) * (d - m)      (torch's lerp)
+ *   v'  = beta2 * v + (w2 * d) * d
+ *   den = sqrt(v') / bc2_sqrt + eps
+ *   p'  = p0 + (-step_size) * (m' / den)
+ * amsgrad, maximize and capturable are not served. */
+typedef struct psgd_adam_hyper {
+    float w1;        /* 1 - beta1 */
+    float beta2, w2; /* w2 = 1 - beta2 */
+    float eps;
+    float step_size; /* lr / (1 - beta1^t) */
+    float bc2_sqrt;  /* sqrt(1 - beta2^t) */
+    float weight_decay;
+    float decay;     /* 1 - lr * weight_decay */
+    int32_t decoupled;
+} psgd_adam_hyper;
+
+/* psgd_adam_update: THE UPDATE, element-wise, in one launch (k_adam_update) over `count` tensors
+ * given as host arrays of device pointers: g[i] the averages (read only), p[i] the weights, m[i] /
+ * v[i] the first and second moments (torch's exp_avg / exp_avg_sq), numel[i] dense fp32 elements
+ * each, hyper[i] the tensor's record. Each of the four pointers is 4-byte aligned or better,
+ * independently: a work item (at most 4096 elements of one tensor, 64-bit offsets) whose four
+ * first addresses agree modulo 16 bytes runs as a head of 0-3 elements, 16-byte vectors and a tail,
+ * any other as 4-byte accesses; every load is issued before the first store and every access goes
+ * through a descriptor of the item's own elements. Nothing outside the numel elements of p[i] /
+ * m[i] / v[i] is written. Also the second half of a destination or slab step, as psgd_sgd_update.
+ * `plan`: as for psgd_sgd_update (a bound plan keeps the change-detected tables on the device and
+ * the host never waits; NULL: uploaded and the launch awaited).
+ * Refusals, in this order, all before any launch: a null g / p / m / v / numel / hyper or count < 1:
+ * PSGD_ERR_VALUE; a plan that is not bound: PSGD_ERR_STATE; a null g[i] / p[i] / m[i] / v[i],
+ * numel[i] < 0: PSGD_ERR_VALUE; a pointer that is not 4-byte aligned: PSGD_ERR_LAYOUT. */
+int psgd_adam_update(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* m,
+                     void* const* v, const int64_t* numel, const psgd_adam_hyper* hyper, void* stream);
+
+/* psgd_aggregate_comm_adam: the world-size-W step whose final pass, at the element where it would
+ * have stored an average, applies THE UPDATE to the weight and both moments instead: the n x m
+ * averages never exist in memory and no optimizer pass follows. DEFINED as this sequence and equal
+ * to it bit for bit (every p, m, v, residual, P/Q state; the same collectives in order and count):
+ *   1. psgd_aggregate_comm_dst(plan, grads, dst, step, flat, unc, unc_dst, comm) into scratch
+ *      destinations
+ *   2. psgd_adam_update on those averages with params / ms / vs (then unc_params / unc_ms / unc_vs)
+ * `params`, `ms`, `vs` are in the plan's tensor order, `unc_*` in the flat plan's; `hyper` holds the
+ * plan's tensors' records, then the flat plan's. `comm` NULL: world size 1, no collectives.
+ * Where it runs: the final pass of step 1 as its Adam instance (psgd_adam_dst.hip: k_apply_adam,
+ * k_lowrank_adam): tiles, loads, LDS staging, the MFMA sequence, alpha x the accumulators and the
+ * residual store are the destination instance's, so g has the same bits. A tile takes 16-byte
+ * accesses where its first element is 16-byte aligned in p, m and v, else 4-byte ones, chosen once
+ * per tile; p, m and v each go through a descriptor over the tile's rows of that tensor alone. The
+ * stores of p', m' and v' are plain. The record is read once per tile, workgroup-uniformly. The
+ * flat tail is staged and summed as in step 1; the leading workgroups of the final launch apply THE
+ * UPDATE to the flat plan's tensors from the stage.
+ * Eligible: psgd_plan_dst_ok's rule, and the Adam instances of the plan's final passes admitted too
+ * (two waves per SIMD, no scratch). psgd_plan_adam_ok: *ok = 1 for such a plan. Rank bucket 8 with
+ * 2 or 3 iterations is refused (its destination instances are not admitted either).
+ * Refusals: psgd_aggregate_comm_dst's codes in its order (a null params / ms / vs / hyper: "null
+ * argument"; a p, m or v that is not 4-byte aligned: PSGD_ERR_LAYOUT; a null m[i] / v[i]:
+ * PSGD_ERR_VALUE), all before any launch or collective. */
+int psgd_aggregate_comm_adam(psgd_plan* plan, void* const* grads, void* const* params, void* const* ms,
+                             void* const* vs, const psgd_adam_hyper* hyper, int64_t step, psgd_flat* flat,
+                             void* const* unc, void* const* unc_params, void* const* unc_ms, void* const* unc_vs,
+                             psgd_comm* comm, void* stream);
+int psgd_plan_adam_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
+
 /* ------------------------ global-norm clipping of a step's averages (clip_grad_norm_) ---------- */
 /* torch.nn.utils.clip_grad_norm_ (L2) over everything a step returned, on the stream, with no host
  * synchronisation: norm = sqrt(sum of squares of the compressed averages `out` and of the dense

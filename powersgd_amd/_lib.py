@@ -103,6 +103,9 @@ _SIGNATURES = {
     "psgd_sgd_update": ([_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_aggregate_comm_sgd": ([_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_plan_sgd_ok": ([_vp, _i64, _i32, _i32, _P_i32], _i32),
+    "psgd_adam_update": ([_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_aggregate_comm_adam": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_adam_ok": ([_vp, _i64, _i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -132,6 +135,33 @@ def sgd_update(plan: Optional["Plan"], g, p, buf, numel: Sequence[int], hyper, s
     n = len(numel)
     check(lib().psgd_sgd_update(plan._h if plan is not None else None, n, g, p, buf, (_i64 * max(1, n))(*numel),
                                 ctypes.addressof(hyper), stream))
+
+
+class AdamHyper(ctypes.Structure):  # psgd_adam_hyper (include/psgd.h)
+    _fields_ = [(k, ctypes.c_float) for k in ("w1", "beta2", "w2", "eps", "step_size", "bc2_sqrt", "weight_decay",
+                                              "decay")] + [("decoupled", _i32)]
+
+
+def adam_hyper(records):
+    """A psgd_adam_hyper array from (lr, beta1, beta2, eps, weight_decay, decoupled, t) tuples of Python
+    numbers, ``t`` the tensor's step count after the increment: every scalar in double exactly as
+    torch's ``_single_tensor_adam`` computes it (non-capturable), each rounded to fp32 once, here."""
+    out = (AdamHyper * max(1, len(records)))()
+    for h, (lr, b1, b2, eps, wd, decoupled, t) in zip(out, records):
+        h.w1, h.beta2, h.w2, h.eps = 1 - b1, b2, 1 - b2, eps
+        h.step_size = lr / (1 - b1 ** t)
+        h.bc2_sqrt = (1 - b2 ** t) ** 0.5
+        h.weight_decay, h.decay, h.decoupled = wd, 1 - lr * wd, int(bool(decoupled))
+    return out
+
+
+def adam_update(plan: Optional["Plan"], g, p, m, v, numel: Sequence[int], hyper, stream: int) -> None:
+    """psgd_adam_update: the element-wise Adam / AdamW update over ``len(numel)`` tensors. ``g`` / ``p`` /
+    ``m`` / ``v``: addresses of host arrays of device pointers; ``hyper`` from ``adam_hyper``. ``plan``
+    (bound) keeps the tables on the device; None: uploaded and awaited."""
+    n = len(numel)
+    check(lib().psgd_adam_update(plan._h if plan is not None else None, n, g, p, m, v, (_i64 * max(1, n))(*numel),
+                                 ctypes.addressof(hyper), stream))
 
 
 _lib = None
@@ -367,6 +397,23 @@ class Plan:
         check(lib().psgd_aggregate_comm_sgd(self._h, grads, params, bufs, ctypes.addressof(hyper) if hyper is not None
                                             else None, step, flat._h if flat is not None else None, unc, unc_params,
                                             unc_bufs, comm._h if comm is not None else None, stream))
+
+    # --- the fused Adam / AdamW step
+    def adam_ok(self, step: int, world: int) -> int:
+        """1 where ``aggregate_comm_adam`` serves this plan (psgd_plan_adam_ok: ``dst_ok``'s rule and the
+        Adam instances admitted), 0 for a plan it refuses."""
+        ok = _i32()
+        check(lib().psgd_plan_adam_ok(self._h, step, world, ctypes.byref(ok)))
+        return int(ok.value)
+
+    def aggregate_comm_adam(self, grads, params, ms, vs, hyper, step: int, comm: Optional["Comm"], stream: int,
+                            flat=None, unc=None, unc_params=None, unc_ms=None, unc_vs=None) -> None:
+        """psgd_aggregate_comm_adam: ``aggregate_comm_dst`` followed by ``adam_update`` in one call; the final
+        pass updates ``params[i]`` / ``ms[i]`` / ``vs[i]`` (then the flat plan's) and stores no average.
+        ``hyper``: ``adam_hyper`` records, the plan's tensors then the flat plan's."""
+        check(lib().psgd_aggregate_comm_adam(self._h, grads, params, ms, vs, ctypes.addressof(hyper) if hyper is not None
+                                             else None, step, flat._h if flat is not None else None, unc, unc_params,
+                                             unc_ms, unc_vs, comm._h if comm is not None else None, stream))
 
     def aggregate_ipc_dst(self, grads, dst, step: int, stream: int, flat=None, unc=None, unc_dst=None) -> None:
         """psgd_aggregate_ipc_dst: the same over the plan's open exchange session (``aggregate_ipc``)."""

@@ -655,10 +655,13 @@ constexpr int kLowrankUR = PSGD_LOWRANK_UR;
 // a.odst[d.tensor], a tensor of any 2-byte alignment; the store form as in apply_tile (psgd_stream.cuh).
 // T = float (psgd_aggregate_comm_dst): a tensor of any 4-byte alignment, st_vec_dstf's forms
 // kDstSgdVec / kDstSgdElem (psgd_aggregate_comm_sgd, T = float): the update forms, as in apply_tile
+// kDstAdamVec / kDstAdamElem (psgd_aggregate_comm_adam): the Adam forms; this tile caches P rows
+// only (61-129 VGPRs as an SGD form), so p, m and v all go out ahead of the row's term chain
 template <typename T, int R, int NI, int V, int DST = 0>
 __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t,
-                                             const SgdTile* sg = nullptr) {
-    constexpr bool SGD = DST >= kDstSgdVec;
+                                             const SgdTile* sg = nullptr, const AdamTile* ad = nullptr) {
+    constexpr bool SGD = is_sgd_dst(DST);
+    constexpr bool ADAM = is_adam_dst(DST);
     const TileGeom g = tile_geom<V>(d, t);
     const int r = d.r;
     T* obase;
@@ -668,6 +671,11 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
                                 uint32_t((g.row_end - g.row_begin) * g.m * int64_t(sizeof(T))));
     rsrc_t rB = rO;
     if constexpr (SGD) rB = sgd_buf_rsrc(*sg, g.row_begin * g.m, uint32_t((g.row_end - g.row_begin) * g.m * 4));
+    rsrc_t rM = rO, rV = rO;
+    if constexpr (ADAM) {
+        rM = make_rsrc(ad->m + g.row_begin * g.m, uint32_t((g.row_end - g.row_begin) * g.m * 4));
+        rV = make_rsrc(ad->v + g.row_begin * g.m, uint32_t((g.row_end - g.row_begin) * g.m * 4));
+    }
     const int nt = NI > 0 ? NI : a.nterms;
     constexpr int NC = NI > 0 ? NI : 1;
     float ba[NC][V][R];
@@ -703,6 +711,13 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
                     sgd_ld<DST>(rO, so, pv);
                     sgd_ld<DST>(rB, so, bv);
                 }
+                float vv[V];
+                if constexpr (ADAM) {
+                    const uint32_t so = uint32_t(((row < g.row_end ? row : row0) - g.row_begin) * g.m + g.col0) * 4u;
+                    sgd_ld<adam_io<DST>()>(rO, so, pv);
+                    sgd_ld<adam_io<DST>()>(rM, so, bv);
+                    sgd_ld<adam_io<DST>()>(rV, so, vv);
+                }
 #pragma unroll
                 for (int k = 0; k < NI; ++k)
 #pragma unroll
@@ -710,6 +725,7 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
                 if (g.active && row < g.row_end) {
                     const uint32_t off = uint32_t((row - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(T));
                     if constexpr (SGD) sgd_apply<DST, V>(*sg, rO, rB, off, o, pv, bv);
+                    else if constexpr (ADAM) adam_apply<DST, V>(*ad, rO, rM, rV, off, o, pv, bv, vv);
                     else if constexpr (DST != 0 && std::is_same<T, float>::value) st_vec_dstf<DST>(rO, off, o);
                     else if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
                     else st_vec<T>(rO, off, o);
@@ -729,6 +745,13 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
             sgd_ld<DST>(rO, so, pv);
             sgd_ld<DST>(rB, so, bv);
         }
+        float vv[V];
+        if constexpr (ADAM) {
+            const uint32_t so = uint32_t((row - g.row_begin) * g.m + g.col0) * 4u;
+            sgd_ld<adam_io<DST>()>(rO, so, pv);
+            sgd_ld<adam_io<DST>()>(rM, so, bv);
+            sgd_ld<adam_io<DST>()>(rV, so, vv);
+        }
         for (int k = 0; k < nt; ++k) {
             float aa[R];
             ld_factor<R>(gconst<float>(a.apx.p[k]) + d.poff + prow, r, aa);
@@ -747,6 +770,7 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
         if (g.active) {
             const uint32_t off = uint32_t((row - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(T));
             if constexpr (SGD) sgd_apply<DST, V>(*sg, rO, rB, off, o, pv, bv);
+            else if constexpr (ADAM) adam_apply<DST, V>(*ad, rO, rM, rV, off, o, pv, bv, vv);
             else if constexpr (DST != 0 && std::is_same<T, float>::value) st_vec_dstf<DST>(rO, off, o);
             else if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
             else st_vec<T>(rO, off, o);

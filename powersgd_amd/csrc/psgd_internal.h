@@ -587,6 +587,36 @@ struct SgdArgs {
 };
 hipError_t launch_sgd_update(const SgdArgs& a, hipStream_t s);
 
+// psgd_aggregate_comm_adam: the same with the Adam update (include/psgd.h, THE UPDATE of
+// psgd_adam_hyper). The parameter table is ApplyArgs::odst; here the two moment tables (the plan's
+// tensor order), the flat plan's parameters and moments, the staged flat tail, and the records.
+struct AdamDst {
+    void* const* ms;
+    void* const* vs;
+    void* const* unc_p;
+    void* const* unc_m;
+    void* const* unc_v;
+    const float* stage;
+    const psgd_adam_hyper* hyper;
+    int32_t unc0;
+};
+// psgd_adam_dst.hip: the Adam instances of launch_apply_dst / launch_lowrank_dst, and the
+// element-wise k_adam_update (SgdItem work items)
+hipError_t launch_apply_adam(int R, int nterms, bool shared, const ApplyArgs& a, const AdamDst& x, int ntiles,
+                             hipStream_t s, int* waves);
+hipError_t launch_lowrank_adam(int R, int nterms, const ApplyArgs& a, const AdamDst& x, int ntiles, hipStream_t s,
+                               int* waves);
+struct AdamArgs {
+    const SgdItem* items;
+    void* const* g;  // per tensor: the averages, the weights, the two moments
+    void* const* p;
+    void* const* m;
+    void* const* v;
+    const psgd_adam_hyper* hyper;
+    int32_t nitems;
+};
+hipError_t launch_adam_update(const AdamArgs& a, hipStream_t s);
+
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),
 // then two parities x iterations slots of xchg_slot floats each; the producer kernels (k_reduce,

@@ -17,6 +17,8 @@
 //   fp32 update  psgd_aggregate_comm_sgd: psgd_aggregate_comm_dst into scratch destinations, then
 //                psgd_sgd_update on them; the final pass applies the SGD update to the weights and the
 //                momentum buffers at the element where it would have stored the average.
+//   fp32 adam    psgd_aggregate_comm_adam: the same with psgd_adam_update (torch's Adam / AdamW rule on
+//                the weights and both moments).
 // Every entry is a descriptor (Entry) and its arguments (Call): one preamble runs the checks in the
 // entry's documented order, one body makes the side state, asks admission (a refusal launches
 // nothing), builds the sink and hands it to the step driver of the entry's transport.
@@ -34,7 +36,9 @@ struct Entry {
     bool wide, tables, bf16;
     bool sgd = false;  // the update sink: `peer` the parameters, Call::bufs / hyper beside them; a null
                        // communicator is world size 1 without collectives
-    Adm::Kind kind() const { return sgd ? Adm::F32Sgd : !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense; }
+    bool adam = false;  // the Adam update sink: Call::bufs / vs the two moments, Call::adam the records
+    bool upd() const { return sgd || adam; }
+    Adm::Kind kind() const { return adam ? Adm::F32Adam : sgd ? Adm::F32Sgd : !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense; }
 };
 
 // The arguments by role. `state`: the fp32 tensors the codec runs on (a bf16 sink: the residual; else
@@ -57,16 +61,27 @@ struct Call {
     void* const* bufs = nullptr;
     void* const* unc_bufs = nullptr;
     const psgd_sgd_hyper* hyper = nullptr;
+    // the Adam sink: `bufs` / `unc_bufs` the first moments, these the second, and its records
+    void* const* vs = nullptr;
+    void* const* unc_vs = nullptr;
+    const psgd_adam_hyper* adam = nullptr;
 };
 
 // The plans an entry serves, by shape. bf16 sinks: fp32, one bucket, rank buckets 1 / 2 / 4 (VALU
 // tiles) and 16 / 32 (matrix-core tiles, psgd_mixed_mfma.hip), not 8 (the VALU tile whose
 // register-cached two-set instances sit at the scratch edge); the wide entries: what those refuse by
 // rank. fp32 tables: fp32, one bucket, not wide
-const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool sgd = false) {
+const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool sgd = false, bool adam = false) {
     *code = PSGD_ERR_VALUE;
     const int rb = p->rbucket;
-    if (sgd) {
+    if (adam) {
+        if (p->dtype != PSGD_F32) {
+            *code = PSGD_ERR_DTYPE;
+            return "psgd_aggregate_comm_adam takes an fp32 plan";
+        }
+        if (p->wide()) return "psgd_aggregate_comm_adam serves rank buckets 1 to 32";
+        if (p->spans.size() > 1) return "psgd_aggregate_comm_adam takes a plan of one bucket";
+    } else if (sgd) {
         if (p->dtype != PSGD_F32) {
             *code = PSGD_ERR_DTYPE;
             return "psgd_aggregate_comm_sgd takes an fp32 plan";
@@ -104,8 +119,9 @@ const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool
 bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
     OutSink sink;
     sink.sgd = kind == Adm::F32Sgd;
-    sink.bf16 = kind != Adm::F32Tables && !sink.sgd;
-    sink.tables = kind == Adm::Bf16Tables || kind == Adm::F32Tables || sink.sgd;
+    sink.adam = kind == Adm::F32Adam;
+    sink.bf16 = kind != Adm::F32Tables && !sink.sgd && !sink.adam;
+    sink.tables = kind == Adm::Bf16Tables || kind == Adm::F32Tables || sink.sgd || sink.adam;
     const int world = comm == Adm::Many ? 2 : 1;
     int w = 0;
     hipError_t e = hipErrorInvalidValue;
@@ -151,9 +167,9 @@ bool admitted(psgd_plan* p, Adm::Kind kind, Adm::Comm comm) {
 // per communicator kind; the wide entries and the fp32 tables are eligible as a whole plan or not
 bool eligible(psgd_plan* p, const Entry& e, int world) {
     if (e.via == Entry::World1 && !e.wide) return admitted(p, e.kind(), Adm::NoComm);
-    // the update entry is defined as the destination-table step followed by psgd_sgd_update: it serves
-    // the plans whose destination instances are admitted too
-    if (e.sgd && !(admitted(p, Adm::F32Tables, Adm::Many) && admitted(p, Adm::F32Tables, Adm::One))) return false;
+    // an update entry is defined as the destination-table step followed by psgd_sgd_update /
+    // psgd_adam_update: it serves the plans whose destination instances are admitted too
+    if (e.upd() && !(admitted(p, Adm::F32Tables, Adm::Many) && admitted(p, Adm::F32Tables, Adm::One))) return false;
     if (e.wide || !e.bf16) return admitted(p, e.kind(), Adm::Many) && admitted(p, e.kind(), Adm::One);
     return admitted(p, e.kind(), world == 1 ? Adm::One : Adm::Many);
 }
@@ -215,8 +231,8 @@ void release(psgd_plan::Side*& slot) {
 // Leaves c.f null where there is no flat tail
 int preamble(const Entry& e, Call& c) {
     const psgd_plan* p = c.p;
-    const bool args = p && c.state && c.peer && (e.tables || c.out) && (e.via != Entry::Comm || c.comm || e.sgd) &&
-                      (!e.sgd || c.hyper);
+    const bool args = p && c.state && c.peer && (e.tables || c.out) && (e.via != Entry::Comm || c.comm || e.upd()) &&
+                      (!e.sgd || c.hyper) && (!e.adam || (c.bufs && c.vs && c.adam));
     if (e.via == Entry::Xchg) {
         if (!args) return fail(PSGD_ERR_VALUE, "null argument");
         if (c.step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
@@ -227,7 +243,7 @@ int preamble(const Entry& e, Call& c) {
     if (!e.tables)
         if (int st = check_out(c.out)) return st;
     int code = PSGD_ERR_VALUE;
-    const char* why = ineligible(p, e.bf16, e.wide, &code, e.sgd);
+    const char* why = ineligible(p, e.bf16, e.wide, &code, e.sgd, e.adam);
     if (why && !e.bf16) return fail(code, why);
     if (!c.f || c.f->total == 0) c.f = nullptr;
     if (const psgd_flat* f = c.f) {
@@ -247,7 +263,7 @@ int preamble(const Entry& e, Call& c) {
     // aligned and the fp32 residual 4-byte; fp32 destinations 4-byte
     const uintptr_t al = e.bf16 ? 2 : 4;
     const char* al_msg = e.bf16  ? "bf16 gradients must be 2-byte aligned"
-                         : e.sgd ? "parameters must be 4-byte aligned"
+                         : e.upd() ? "parameters must be 4-byte aligned"
                                  : "fp32 destinations must be 4-byte aligned";
     for (size_t i = 0; i < p->shapes.size(); ++i) {
         if (!c.state[i] || !c.peer[i]) return fail(PSGD_ERR_VALUE, "null gradient pointer");
@@ -260,6 +276,8 @@ int preamble(const Entry& e, Call& c) {
             if (reinterpret_cast<uintptr_t>(c.unc_peer[i]) % al) return fail(PSGD_ERR_LAYOUT, al_msg);
     if (e.sgd)
         if (int st = sgd_check(p, c.bufs, c.f, c.unc_bufs, c.hyper)) return st;
+    if (e.adam)
+        if (int st = adam_check(p, c.bufs, c.vs, c.f, c.unc_bufs, c.unc_vs)) return st;
     if (e.via == Entry::Xchg) {
         if (int st = ipc_check(p, c.step)) return st;
         if (c.f && c.f->total > p->ipc_flat_cap)
@@ -275,7 +293,8 @@ int body(const Entry& e, const Call& c, bool* refused) {
     psgd_flat* f = c.f;
     hipStream_t s = static_cast<hipStream_t>(c.stream);
     DevScope scope(p->device);
-    if (e.sgd) {  // its tables are psgd_plan::Sgd's (psgd_sgd.cpp), and there is no transport but the communicator
+    if (e.upd()) {  // its tables are psgd_plan::Sgd's / Adam's (psgd_sgd.cpp, psgd_adam.cpp), and there is
+                    // no transport but the communicator
         if (int st = refresh_pointers(p, c.state, s)) return st;
         if (!eligible(p, e, 1)) {
             *refused = true;
@@ -283,7 +302,12 @@ int body(const Entry& e, const Call& c, bool* refused) {
                                                               "(two waves per SIMD, no scratch)");
         }
         OutSink sink;
-        if (int st = sgd_select(p, c.peer, c.bufs, f, c.unc_peer, c.unc_bufs, c.hyper, s, &sink)) return st;
+        if (e.adam) {
+            if (int st = adam_select(p, c.peer, c.bufs, c.vs, f, c.unc_peer, c.unc_bufs, c.unc_vs, c.adam, s, &sink))
+                return st;
+        } else if (int st = sgd_select(p, c.peer, c.bufs, f, c.unc_peer, c.unc_bufs, c.hyper, s, &sink)) {
+            return st;
+        }
         return aggregate_comm_ctx(p, c.state, c.step, f, c.unc_state, c.comm, s, sink);
     }
     psgd_plan::Side*& slot = e.bf16 ? p->mixed : p->direct;
@@ -370,6 +394,7 @@ const Entry kMixedIpcDst{"psgd_aggregate_mixed_ipc_dst", Entry::Xchg, false, tru
 const Entry kCommDst{"psgd_aggregate_comm_dst", Entry::Comm, false, true, false};
 const Entry kIpcDst{"psgd_aggregate_ipc_dst", Entry::Xchg, false, true, false};
 const Entry kCommSgd{"psgd_aggregate_comm_sgd", Entry::Comm, false, true, false, true};
+const Entry kCommAdam{"psgd_aggregate_comm_adam", Entry::Comm, false, true, false, false, true};
 
 }  // namespace
 
@@ -466,6 +491,27 @@ int psgd_aggregate_comm_sgd(psgd_plan* p, void* const* grads, void* const* param
     c.unc_bufs = unc_bufs;
     c.hyper = hyper;
     return run(kCommSgd, c);
+}
+
+int psgd_plan_adam_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, false, false, &code, false, true)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kCommAdam, world) ? 1 : 0; });
+}
+
+int psgd_aggregate_comm_adam(psgd_plan* p, void* const* grads, void* const* params, void* const* ms, void* const* vs,
+                             const psgd_adam_hyper* hyper, int64_t step, psgd_flat* f, void* const* unc,
+                             void* const* unc_params, void* const* unc_ms, void* const* unc_vs, psgd_comm* comm,
+                             void* stream) {
+    Call c{p, grads, params, nullptr, step, f, unc, unc_params, nullptr, comm, stream};
+    c.bufs = ms;
+    c.unc_bufs = unc_ms;
+    c.vs = vs;
+    c.unc_vs = unc_vs;
+    c.adam = hyper;
+    return run(kCommAdam, c);
 }
 
 int psgd_aggregate_mixed_flat(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,

@@ -50,6 +50,7 @@ psgd_plan::~psgd_plan() {
     norm_release(this);
     guard_release(this);
     sgd_release(this);
+    adam_release(this);
     if (xerr_host) (void)hipHostFree(xerr_host);
     if (stamp_buf) (void)hipFree(stamp_buf);
 }

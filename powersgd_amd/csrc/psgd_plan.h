@@ -419,7 +419,8 @@ struct psgd_plan {
     struct Admission {
         enum Kind {
             Bf16Dense, Bf16Tables, F32Tables, Bf16Ingest /* world size 1, the single-pass final kernel */,
-            F32Sgd /* the update instances of psgd_aggregate_comm_sgd */, kKinds
+            F32Sgd /* the update instances of psgd_aggregate_comm_sgd */,
+            F32Adam /* the Adam instances of psgd_aggregate_comm_adam */, kKinds
         };
         enum Comm { NoComm /* aggregate_ctx */, Many /* world size > 1 */, One /* a 1-rank communicator */, kComms };
         uint64_t key = ~uint64_t(0);
@@ -474,6 +475,9 @@ struct psgd_plan {
     // stage of the flat tail), made by the first call
     struct Sgd;
     Sgd* sgd = nullptr;
+    // psgd_adam_update / psgd_aggregate_comm_adam (psgd_adam.cpp): the same for the Adam update
+    struct Adam;
+    Adam* adam = nullptr;
     int64_t xslot_off(int64_t step, int it) const {  // byte offset of a slot in every buffer
         return kXchgHeader + ((step & 1) * iters + it) * ipc_slot * int64_t(sizeof(float));
     }
@@ -586,6 +590,8 @@ namespace psgd {
 //                 parameters; the final pass applies the SGD update there instead of storing the
 //                 average, with the momentum buffers (`bufs`, `unc_bufs`) and the per-tensor records
 //                 (`hyper`: the plan's tensors, then the flat plan's from `hyper_unc0`)
+//   adam          psgd_aggregate_comm_adam: the same with the Adam update; `bufs` / `unc_bufs` are the
+//                 first moments, `vs` / `unc_vs` the second, `adam_hyper` the records
 // A null sink in a context is the plain one: the plan's dtype into StepCtx::out / `out`.
 struct OutSink {
     bool bf16 = false, tables = false;
@@ -602,6 +608,11 @@ struct OutSink {
     const psgd_sgd_hyper* hyper = nullptr;
     int32_t hyper_unc0 = 0;
     SgdDst sgd_dst() const { return SgdDst{bufs, unc_dst, unc_bufs, stage, hyper, hyper_unc0}; }
+    bool adam = false;
+    void* const* vs = nullptr;
+    void* const* unc_vs = nullptr;
+    const psgd_adam_hyper* adam_hyper = nullptr;
+    AdamDst adam_dst() const { return AdamDst{bufs, vs, unc_dst, unc_bufs, unc_vs, stage, adam_hyper, hyper_unc0}; }
     // the flat tail's bf16 gradients are added in the step, (x + float(g)) / W in a launch of its
     // own ahead of every collective; else the tail is packed as psgd_aggregate_comm packs it
     bool ingests() const { return bf16 && !tables; }
@@ -754,6 +765,14 @@ void sgd_release(psgd_plan* p);
 int sgd_check(const psgd_plan* p, void* const* bufs, const psgd_flat* f, void* const* unc_bufs, const psgd_sgd_hyper* hyper);
 int sgd_select(psgd_plan* p, void* const* params, void* const* bufs, const psgd_flat* f, void* const* unc_params,
                void* const* unc_bufs, const psgd_sgd_hyper* hyper, hipStream_t s, OutSink* sink);
+// psgd_adam.cpp: the same for psgd_aggregate_comm_adam (a null moment: PSGD_ERR_VALUE; one that is
+// not 4-byte aligned: PSGD_ERR_LAYOUT)
+void adam_release(psgd_plan* p);
+int adam_check(const psgd_plan* p, void* const* ms, void* const* vs, const psgd_flat* f, void* const* unc_ms,
+               void* const* unc_vs);
+int adam_select(psgd_plan* p, void* const* params, void* const* ms, void* const* vs, const psgd_flat* f,
+                void* const* unc_params, void* const* unc_ms, void* const* unc_vs, const psgd_adam_hyper* hyper,
+                hipStream_t s, OutSink* sink);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
 int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
 // The world-size-W step into `sink`: over a communicator (psgd_step.cpp; `comm` null: world size 1,

@@ -8,55 +8,16 @@
 // misses earlier under a schedule: a copy of a few KiB, long complete, so the wait returns at once).
 #include <cstring>
 
-#include "psgd_plan.h"
+#include "psgd_tables.h"
+
+using psgd::put;
+using psgd::put_ptrs;
+using psgd::WordTable;
 
 namespace {
 
 static_assert(sizeof(psgd_sgd_hyper) == 3 * sizeof(void*), "a record is three table words");
 static_assert(sizeof(psgd::SgdItem) == 2 * sizeof(void*), "a work item is two table words");
-
-struct WordTable {
-    psgd::TableCache t;
-    char* dev = nullptr;
-    size_t cap = 0;
-    // a table of `words` entries: bind, grow or re-bind; launches on `s` may still read the old one
-    int room(size_t words, hipStream_t s) {
-        if (dev && words <= cap && t.n == words) return PSGD_OK;
-        if (dev) PSGD_HIP(hipStreamSynchronize(s));
-        if (!dev || words > cap) {
-            release();
-            PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&dev), psgd::TableCache::bytes(words)));
-            cap = words;
-        }
-        t.bind(dev, words);
-        return PSGD_OK;
-    }
-    // the words' device copy (selected, or uploaded stream-ordered)
-    int select(const std::vector<void*>& words, hipStream_t s, const void** out) {
-        if (int st = room(words.size(), s)) return st;
-        PSGD_HIP(t.select(words.data(), s));
-        *out = t.table();
-        return PSGD_OK;
-    }
-    void release() {
-        t.release();
-        if (dev) (void)hipFree(dev);
-        dev = nullptr;
-        cap = 0;
-    }
-    ~WordTable() { release(); }
-};
-
-void put(std::vector<void*>& w, const void* src, size_t bytes) {
-    const size_t at = w.size();
-    w.resize(at + (bytes + sizeof(void*) - 1) / sizeof(void*), nullptr);
-    if (bytes) std::memcpy(w.data() + at, src, bytes);
-}
-
-void put_ptrs(std::vector<void*>& w, void* const* ptrs, size_t n) {
-    if (ptrs) w.insert(w.end(), ptrs, ptrs + n);
-    else w.resize(w.size() + n, nullptr);
-}
 
 }  // namespace
 

@@ -538,6 +538,9 @@ hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArg
         if (sink->sgd)  // the update applied where the average would have been stored
             return o.kind == OutRoute::Lowrank ? launch_lowrank_sgd(R, I, a, sink->sgd_dst(), ntiles, s, waves)
                                                : launch_apply_sgd(R, I, o.shared, a, sink->sgd_dst(), ntiles, s, waves);
+        if (sink->adam)  // the Adam update likewise
+            return o.kind == OutRoute::Lowrank ? launch_lowrank_adam(R, I, a, sink->adam_dst(), ntiles, s, waves)
+                                               : launch_apply_adam(R, I, o.shared, a, sink->adam_dst(), ntiles, s, waves);
         const DirectDst t = sink->direct();
         return o.kind == OutRoute::Lowrank ? launch_lowrank_dst(R, I, a, t, ntiles, s, waves)
                                            : launch_apply_dst(R, I, o.shared, a, t, ntiles, s, waves);

@@ -324,6 +324,84 @@ __device__ __forceinline__ void sgd_apply(const SgdTile& sg, rsrc_t rP, rsrc_t r
 __device__ __forceinline__ rsrc_t sgd_buf_rsrc(const SgdTile& sg, int64_t first, uint32_t bytes) {
     return make_rsrc(sg.buf ? sg.buf + first : nullptr, sg.buf ? bytes : 0u);
 }
+constexpr bool is_sgd_dst(int dst) { return dst == kDstSgdVec || dst == kDstSgdElem; }
+
+// The Adam update forms (psgd_aggregate_comm_adam, psgd_adam_dst.hip; TO = float): the same place in
+// the tile, with torch's single-tensor Adam / AdamW rule (include/psgd.h, THE UPDATE of
+// psgd_adam_hyper) on the weight and both moments. kDstAdamVec: 16-byte accesses where the tile's
+// first element is 16-byte aligned in p, m and v; kDstAdamElem: four 4-byte ones. m and v are
+// tensors of their own (torch's exp_avg / exp_avg_sq), so each has a descriptor over the tile's rows
+// of that tensor: three descriptors are twelve SGPRs, and the byte offset of a vector is one VGPR
+// shared by p, m and v and formed again at the store. The record is read once per tile from
+// workgroup-uniform addresses; the decay branch and the lerp side are scalar.
+constexpr int kDstAdamVec = 5, kDstAdamElem = 6;
+constexpr bool is_adam_dst(int dst) { return dst == kDstAdamVec || dst == kDstAdamElem; }
+struct AdamTile {
+    float* m;  // the tensor's exp_avg and exp_avg_sq
+    float* v;
+    psgd_adam_hyper h;
+};
+// The only place the formula is written. Every product is a rounded fp32 value of its own
+// (mul_rn), sqrt and the divisions are the correctly rounded ones of the default build
+__device__ __forceinline__ void adam_update(const psgd_adam_hyper& h, float g, float& p, float& m, float& v) {
+    float d = g, p0 = p;
+    if (h.weight_decay != 0.f) {
+        if (h.decoupled) p0 = mul_rn(h.decay, p);
+        else d = g + mul_rn(h.weight_decay, p);
+    }
+    const float dm = d - m;
+    m = h.w1 < 0.5f ? m + mul_rn(h.w1, dm) : d - mul_rn(1.f - h.w1, dm);  // torch's lerp
+    v = mul_rn(h.beta2, v) + mul_rn(mul_rn(h.w2, d), d);
+    const float den = sqrtf(v) / h.bc2_sqrt + h.eps;
+    p = p0 + mul_rn(-h.step_size, m / den);
+}
+// How p, m and v move through a tile ("Fused Adam step"): how many of the
+// three streams are requested ahead of a row's term chain (VALU tiles) or ahead of the block's MFMA
+// chain (matrix-core tiles), in the order p, m, v; the rest are requested at the row's store. And
+// the rows a lane of a VALU tile keeps in flight. Neither changes an element's arithmetic.
+#ifndef PSGD_ADAM_AHEAD
+#define PSGD_ADAM_AHEAD 3
+#endif
+#ifndef PSGD_ADAM_AHEAD_MFMA
+#define PSGD_ADAM_AHEAD_MFMA 3
+#endif
+constexpr int kAdamAhead = PSGD_ADAM_AHEAD, kAdamAheadMfma = PSGD_ADAM_AHEAD_MFMA;
+#ifndef PSGD_ADAM_UR_CACHED
+#define PSGD_ADAM_UR_CACHED 2
+#endif
+// rows in flight per lane of a VALU tile (kUnroll = 4 for every other form): the register-cached
+// two-set instances from 4 factor columns per set on, and the shared ones from 16 on, keep 2
+constexpr int adam_rows_in_flight(int R, int NI, bool shared) {
+    if (NI <= 0) return 4;
+    return R * NI >= (shared ? 16 : 4) ? PSGD_ADAM_UR_CACHED : 4;
+}
+template <int DST>
+__device__ __forceinline__ constexpr int adam_io() {  // the load / store form of the same width
+    return DST == kDstAdamElem ? kDstSgdElem : kDstSgdVec;
+}
+// The epilogue: the averages pinned as sgd_apply pins them (the destination instance's store
+// form), THE UPDATE on the loaded p / m / v, three plain stores
+template <int DST, int V>
+__device__ __forceinline__ void adam_apply(const AdamTile& ad, rsrc_t rP, rsrc_t rM, rsrc_t rV, uint32_t off,
+                                           const float (&o)[V], float (&pv)[V], float (&mv)[V], float (&vv)[V]) {
+    float g[V];
+    if constexpr (V == 4) {
+        typedef unsigned v4u __attribute__((ext_vector_type(4)));
+        v4u x = {__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])};
+        asm volatile("" : "+v"(x));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) g[e] = __uint_as_float(x[e]);
+    } else {
+        uint32_t x = __float_as_uint(o[0]);
+        asm volatile("" : "+v"(x));
+        g[0] = __uint_as_float(x);
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) adam_update(ad.h, g[e], pv[e], mv[e], vv[e]);
+    sgd_st<adam_io<DST>()>(rP, off, pv);
+    sgd_st<adam_io<DST>()>(rM, off, mv);
+    sgd_st<adam_io<DST>()>(rV, off, vv);
+}
 
 template <typename T>
 struct Io;
@@ -1309,13 +1387,18 @@ hipError_t dispatch_odd_mfma(int R, int nres, const ProductArgs& a, int ntiles, 
 // four 4-byte stores (st_vec_dstf, dst_al16).
 template <typename T, int R, int NI, bool SHARED, int V, bool ONT = false, typename TO = T, int DST = 0>
 __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t,
-                                           const SgdTile* sg = nullptr) {
-    constexpr bool SGD = DST >= kDstSgdVec;  // the update forms: rO spans the tile's rows of p, rB of buf
+                                           const SgdTile* sg = nullptr, const AdamTile* ad = nullptr) {
+    constexpr bool SGD = is_sgd_dst(DST);  // the update forms: rO spans the tile's rows of p, rB of buf
+    constexpr bool ADAM = is_adam_dst(DST);  // rO spans p, rM / rV the two moments
     // rows in flight per lane. The update forms of the two-set instances that cache 12 or more
     // factor columns per set keep 2: their destination twins sit at the register edge with 4
     // (k_apply_dst<4, 3, false>: 255 VGPRs), and p, buf and the update's temporaries do not fit
     // beside them in two waves per SIMD. Rows are independent: no element's arithmetic changes
-    constexpr int UR = SGD && NI > 0 && !SHARED && R * NI >= 12 ? 2 : kUnroll;
+    // The Adam forms carry a third state stream and the sqrt / divide expansions: every register-
+    // cached two-set instance from 4 factor columns per set on, and the shared ones from 16 on,
+    // keep 2 (adam_rows_in_flight; the table in profiles/adam_step/resources.txt)
+    constexpr int UR = ADAM ? adam_rows_in_flight(R, NI, SHARED)
+                            : SGD && NI > 0 && !SHARED && R * NI >= 12 ? 2 : kUnroll;
     const TileGeom g = tile_geom<V>(d, t);
     const int r = d.r;
     const gptr<T> G = gmut<T>(a.grads[t.tensor]);
@@ -1328,6 +1411,11 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
     const rsrc_t rO = make_rsrc(Op + g.row_begin * g.m, uint32_t((g.row_end - g.row_begin) * g.m * int64_t(sizeof(TO))));
     rsrc_t rB = rO;
     if constexpr (SGD) rB = sgd_buf_rsrc(*sg, g.row_begin * g.m, tb);
+    rsrc_t rM = rO, rV = rO;
+    if constexpr (ADAM) {
+        rM = make_rsrc(ad->m + g.row_begin * g.m, tb);
+        rV = make_rsrc(ad->v + g.row_begin * g.m, tb);
+    }
     const int nt = NI > 0 ? NI : a.nterms;
     constexpr int NC = NI > 0 ? NI : 1;
     constexpr int NA = (NI > 0 && !SHARED) ? NI : 1;
@@ -1388,6 +1476,14 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
                 sgd_ld<DST>(rO, so, pv);
                 sgd_ld<DST>(rB, so, bv);
             }
+            // the Adam forms: the first kAdamAhead of p, m, v go out here, the rest after the chain
+            float vv[V];
+            if constexpr (ADAM) {
+                const uint32_t so = uint32_t((b.rc[u] - g.row_begin) * g.m + g.col0) * uint32_t(sizeof(float));
+                if constexpr (kAdamAhead >= 1) sgd_ld<adam_io<DST>()>(rO, so, pv);
+                if constexpr (kAdamAhead >= 2) sgd_ld<adam_io<DST>()>(rM, so, bv);
+                if constexpr (kAdamAhead >= 3) sgd_ld<adam_io<DST>()>(rV, so, vv);
+            }
             for (int k = 0; k < nt; ++k) {
                 float ap[R], aa[R];
                 if constexpr (NI > 0) {
@@ -1428,9 +1524,14 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
             if (g.active && row + u * g.stride < g.row_end) {
                 const uint32_t eo = uint32_t((b.rc[u] - g.row_begin) * g.m + g.col0);
                 st_vec<T>(rD, eo * uint32_t(sizeof(T)), b.x[u]);
-                if constexpr (SGD)
+                if constexpr (SGD) {
                     sgd_apply<DST, V>(*sg, rO, rB, eo * uint32_t(sizeof(float)), o, pv, bv);
-                else if constexpr (DST != 0 && std::is_same<TO, float>::value)
+                } else if constexpr (ADAM) {
+                    if constexpr (kAdamAhead < 1) sgd_ld<adam_io<DST>()>(rO, eo * 4u, pv);
+                    if constexpr (kAdamAhead < 2) sgd_ld<adam_io<DST>()>(rM, eo * 4u, bv);
+                    if constexpr (kAdamAhead < 3) sgd_ld<adam_io<DST>()>(rV, eo * 4u, vv);
+                    adam_apply<DST, V>(*ad, rO, rM, rV, eo * 4u, o, pv, bv, vv);
+                } else if constexpr (DST != 0 && std::is_same<TO, float>::value)
                     st_vec_dstf<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
                 else if constexpr (DST != 0)
                     st_vec_dst<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
@@ -1475,8 +1576,9 @@ struct ApplyMfmaLds {
 // are the fp32 instance's.
 template <typename T, int R, bool SHARED, bool ONT, int DST = 0, typename TO = T>
 __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDesc& d, const Tile& t, float* qs,
-                                                const SgdTile* sg = nullptr) {
-    constexpr bool SGD = DST >= kDstSgdVec;  // the update forms (T = TO = float): rO spans p, rB buf
+                                                const SgdTile* sg = nullptr, const AdamTile* ad = nullptr) {
+    constexpr bool SGD = is_sgd_dst(DST);  // the update forms (T = TO = float): rO spans p, rB buf
+    constexpr bool ADAM = is_adam_dst(DST);  // rO spans p, rM / rV the two moments
     constexpr int KQ = R / 4;
     constexpr int RP = ApplyMfmaLds<R>::RP;
     constexpr int NS = SHARED ? 1 : 2;
@@ -1525,6 +1627,11 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
     const rsrc_t rO = make_rsrc(Op + row_begin * m, uint32_t((row_end - row_begin) * int64_t(m) * int64_t(sizeof(TO))));
     rsrc_t rB = rO;
     if constexpr (SGD) rB = sgd_buf_rsrc(*sg, row_begin * m, tb);
+    rsrc_t rM = rO, rV = rO;
+    if constexpr (ADAM) {
+        rM = make_rsrc(ad->m + row_begin * m, tb);
+        rV = make_rsrc(ad->v + row_begin * m, tb);
+    }
     const uint32_t cofs = active ? uint32_t(col) * s : kOob;
     const uint32_t rstride = uint32_t(m) * s;
     const bool pvec = r == R && (d.poff & 3) == 0;
@@ -1536,12 +1643,23 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
         for (int v = 0; v < 4; ++v) BufIo<T>::ld4(rG, (rb + v) * rstride + cofs, x[v]);
         // the update forms: the block's p and buf quads go out with the gradient's, ahead of the
         // staging reads and the MFMA chain; the offsets are formed again at the stores
-        float pv[SGD ? 4 : 1][4], bv[SGD ? 4 : 1][4];
+        float pv[SGD || ADAM ? 4 : 1][4], bv[SGD || ADAM ? 4 : 1][4];
         if constexpr (SGD) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 sgd_ld<DST>(rO, (rb + v) * rstride + cofs, pv[v]);
                 sgd_ld<DST>(rB, (rb + v) * rstride + cofs, bv[v]);
+            }
+        }
+        // the Adam forms: the first kAdamAheadMfma of the block's p, m, v quads go out here, the
+        // rest after the MFMA chain, at the row's store
+        float vv[ADAM ? 4 : 1][4];
+        if constexpr (ADAM) {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                if constexpr (kAdamAheadMfma >= 1) sgd_ld<adam_io<DST>()>(rO, (rb + v) * rstride + cofs, pv[v]);
+                if constexpr (kAdamAheadMfma >= 2) sgd_ld<adam_io<DST>()>(rM, (rb + v) * rstride + cofs, bv[v]);
+                if constexpr (kAdamAheadMfma >= 3) sgd_ld<adam_io<DST>()>(rV, (rb + v) * rstride + cofs, vv[v]);
             }
         }
         const int64_t pi = b0 + ri < row_end ? b0 + ri : row_begin;  // A-operand row (clamped)
@@ -1609,6 +1727,11 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
                 else st_vec<TO, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, oo_off, oo);
             } else if constexpr (SGD) {
                 sgd_apply<DST, 4>(*sg, rO, rB, off, oo, pv[v], bv[v]);
+            } else if constexpr (ADAM) {
+                if constexpr (kAdamAheadMfma < 1) sgd_ld<adam_io<DST>()>(rO, off, pv[v]);
+                if constexpr (kAdamAheadMfma < 2) sgd_ld<adam_io<DST>()>(rM, off, bv[v]);
+                if constexpr (kAdamAheadMfma < 3) sgd_ld<adam_io<DST>()>(rV, off, vv[v]);
+                adam_apply<DST, 4>(*ad, rO, rM, rV, off, oo, pv[v], bv[v], vv[v]);
             } else if constexpr (DST != 0) {
                 st_vec_dstf<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, oo);
             } else {

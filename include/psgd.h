@@ -780,6 +780,58 @@ int psgd_aggregate_comm_adam(psgd_plan* plan, void* const* grads, void* const* p
                              psgd_comm* comm, void* stream);
 int psgd_plan_adam_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
 
+/* ------- the fused AdamW step of a bf16 model with fp32 master weights and fp32 moments ------- */
+/* psgd_adam_update_mp: psgd_adam_update plus w_bf16[i][e] = bf16(p'[e]), in one launch
+ * (k_adam_update_mp): p[i] are the fp32 master weights, w_bf16[i] the bf16 model tensors of numel[i]
+ * elements each. The rounding is psgd_runs_gather's conversion from fp32 to bf16: round to nearest
+ * even of the stored fp32 p'. The same work items (at most 4096 elements, 64-bit offsets). The vector
+ * form applies to an item where g, p, m, v agree modulo 16 bytes and w is 8-byte aligned at the
+ * element where they reach their 16-byte boundary (16-byte accesses, 8-byte stores of w); any other
+ * item runs as 4-byte accesses with 2-byte stores of w. Every access goes through a descriptor over
+ * the item's own elements and every load is issued before the first store: nothing outside the numel
+ * elements of p[i] / m[i] / v[i] / w_bf16[i] is written, g is only read.
+ * Refusals: psgd_adam_update's, in its order; a null w_bf16 with the null arguments, a null
+ * w_bf16[i] with the null tensor pointers (PSGD_ERR_VALUE); a w_bf16[i] that is not 2-byte aligned:
+ * PSGD_ERR_LAYOUT. */
+int psgd_adam_update_mp(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* m,
+                        void* const* v, void* const* w_bf16, const int64_t* numel, const psgd_adam_hyper* hyper,
+                        void* stream);
+
+/* psgd_aggregate_mixed_comm_adam: the step of a bf16 model whose optimizer runs on fp32 master
+ * weights, in one call. bf16 gradients feed the fp32 error-feedback residual (Fp32ResidualPowerSGD);
+ * the final pass of the codec, at the element where it would have stored the average, applies THE
+ * UPDATE to the master weight and both moments, stores all three and stores the new weight rounded
+ * to bf16 at the model parameter's own address. No average (fp32 or bf16), no master gradient and
+ * no master-to-model copy exists in memory. DEFINED as this sequence and equal to it bit for bit
+ * (every master, moment, bf16 weight, residual, P/Q state, the zeroed gradients; the same
+ * collectives in order and count):
+ *   1. the ADD over every tensor: residual += float(g); g = +0.0 (psgd_runs_add_list, zero_source)
+ *   2. psgd_aggregate_comm_dst(plan, residual, dst, step, flat, unc_residual, unc_dst, comm) into
+ *      scratch destinations
+ *   3. psgd_adam_update_mp on those averages with masters / ms / vs / params_bf16 (then the unc_*)
+ * Tables are in the plan's tensor order, `unc_*` in the flat plan's; `hyper` holds the plan's tensors'
+ * records, then the flat plan's. `comm` NULL: world size 1, no collectives.
+ * Where it runs: the ADD is the first launch (two where there is a flat tail); the final pass of
+ * step 2 as its master-weight instance (psgd_adam_mp_dst.hip: k_apply_adam_mp, k_lowrank_adam_mp),
+ * psgd_aggregate_comm_adam's with a fourth descriptor over the tile's rows of the model tensor in
+ * 2-byte elements. A tile takes 16-byte accesses and one 8-byte store of w per row quad where its
+ * first element is 16-byte aligned in p, m, v and 8-byte aligned in w, else 4-byte accesses and four
+ * 2-byte stores of w; chosen once per tile. The leading workgroups of the final launch apply THE
+ * UPDATE to the flat plan's tensors from the stage.
+ * Eligible: psgd_plan_adam_ok's rule, and the master-weight instances of the plan's final passes
+ * admitted too (two waves per SIMD, no scratch; asked of the runtime once per plan and tiling).
+ * psgd_plan_mixed_adam_ok: *ok = 1 for such a plan. Rank bucket 8 with 2 or 3 iterations is refused.
+ * A refusal launches nothing and issues no collective.
+ * Refusals: psgd_aggregate_comm_adam's codes in its order (`residual` its grads, `masters` its
+ * params; a null grads_bf16 / params_bf16: "null argument"), then a null bf16 gradient or model
+ * parameter: PSGD_ERR_VALUE, one that is not 2-byte aligned: PSGD_ERR_LAYOUT. */
+int psgd_aggregate_mixed_comm_adam(psgd_plan* plan, void* const* grads_bf16, void* const* residual,
+                                   void* const* params_bf16, void* const* masters, void* const* ms, void* const* vs,
+                                   const psgd_adam_hyper* hyper, int64_t step, psgd_flat* flat, void* const* unc_bf16,
+                                   void* const* unc_residual, void* const* unc_params_bf16, void* const* unc_masters,
+                                   void* const* unc_ms, void* const* unc_vs, psgd_comm* comm, void* stream);
+int psgd_plan_mixed_adam_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
+
 /* ------------------------ global-norm clipping of a step's averages (clip_grad_norm_) ---------- */
 /* torch.nn.utils.clip_grad_norm_ (L2) over everything a step returned, on the stream, with no host
  * synchronisation: norm = sqrt(sum of squares of the compressed averages `out` and of the dense

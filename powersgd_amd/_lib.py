@@ -106,6 +106,9 @@ _SIGNATURES = {
     "psgd_adam_update": ([_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_aggregate_comm_adam": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_plan_adam_ok": ([_vp, _i64, _i32, _P_i32], _i32),
+    "psgd_adam_update_mp": ([_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_aggregate_mixed_comm_adam": ([_vp] * 8 + [_i64] + [_vp] * 9, _i32),
+    "psgd_plan_mixed_adam_ok": ([_vp, _i64, _i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -162,6 +165,14 @@ def adam_update(plan: Optional["Plan"], g, p, m, v, numel: Sequence[int], hyper,
     n = len(numel)
     check(lib().psgd_adam_update(plan._h if plan is not None else None, n, g, p, m, v, (_i64 * max(1, n))(*numel),
                                  ctypes.addressof(hyper), stream))
+
+
+def adam_update_mp(plan: Optional["Plan"], g, p, m, v, w_bf16, numel: Sequence[int], hyper, stream: int) -> None:
+    """psgd_adam_update_mp: ``adam_update`` on fp32 master weights ``p``, and ``w_bf16[i] = bf16(p'[i])`` for
+    the bf16 model tensors, in the same launch."""
+    n = len(numel)
+    check(lib().psgd_adam_update_mp(plan._h if plan is not None else None, n, g, p, m, v, w_bf16,
+                                    (_i64 * max(1, n))(*numel), ctypes.addressof(hyper), stream))
 
 
 _lib = None
@@ -414,6 +425,26 @@ class Plan:
         check(lib().psgd_aggregate_comm_adam(self._h, grads, params, ms, vs, ctypes.addressof(hyper) if hyper is not None
                                              else None, step, flat._h if flat is not None else None, unc, unc_params,
                                              unc_ms, unc_vs, comm._h if comm is not None else None, stream))
+
+    # --- the fused Adam / AdamW step of a bf16 model with fp32 master weights
+    def mixed_adam_ok(self, step: int, world: int) -> int:
+        """1 where ``aggregate_mixed_comm_adam`` serves this plan (psgd_plan_mixed_adam_ok: ``adam_ok``'s rule
+        and the master-weight instances admitted), 0 for a plan it refuses."""
+        ok = _i32()
+        check(lib().psgd_plan_mixed_adam_ok(self._h, step, world, ctypes.byref(ok)))
+        return int(ok.value)
+
+    def aggregate_mixed_comm_adam(self, grads_bf16, residual, params_bf16, masters, ms, vs, hyper, step: int,
+                                  comm: Optional["Comm"], stream: int, flat=None, unc_bf16=None, unc_residual=None,
+                                  unc_params_bf16=None, unc_masters=None, unc_ms=None, unc_vs=None) -> None:
+        """psgd_aggregate_mixed_comm_adam: the ADD of the bf16 gradients into ``residual``,
+        ``aggregate_comm_dst`` on it and ``adam_update_mp`` in one call: the final pass updates
+        ``masters[i]`` / ``ms[i]`` / ``vs[i]`` and stores ``params_bf16[i] = bf16(masters[i])``."""
+        check(lib().psgd_aggregate_mixed_comm_adam(
+            self._h, grads_bf16, residual, params_bf16, masters, ms, vs,
+            ctypes.addressof(hyper) if hyper is not None else None, step, flat._h if flat is not None else None,
+            unc_bf16, unc_residual, unc_params_bf16, unc_masters, unc_ms, unc_vs,
+            comm._h if comm is not None else None, stream))
 
     def aggregate_ipc_dst(self, grads, dst, step: int, stream: int, flat=None, unc=None, unc_dst=None) -> None:
         """psgd_aggregate_ipc_dst: the same over the plan's open exchange session (``aggregate_ipc``)."""

@@ -29,6 +29,19 @@ from .sgd import _comm_or_none
 from .utils import params_in_optimizer
 
 
+def _options_served(optimizer: torch.optim.Optimizer) -> bool:
+    """Exactly ``torch.optim.Adam`` / ``AdamW`` with the options THE UPDATE covers and Python-number
+    hyperparameters."""
+    if type(optimizer) not in (torch.optim.Adam, torch.optim.AdamW):
+        return False
+    for g in optimizer.param_groups:
+        if g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable") or g.get("fused"):
+            return False
+        if any(torch.is_tensor(g[k]) for k in ("lr", "eps", "weight_decay")) or any(map(torch.is_tensor, g["betas"])):
+            return False
+    return True
+
+
 def adam_step_applies(optimizer: torch.optim.Optimizer, aggregator: Aggregator) -> bool:
     """The NEXT ``adam_step`` takes the one-call form: exactly ``torch.optim.Adam`` or ``AdamW`` with
     ``amsgrad``, ``maximize``, ``capturable`` and ``differentiable`` off and ``fused`` not on, fp32
@@ -36,13 +49,8 @@ def adam_step_applies(optimizer: torch.optim.Optimizer, aggregator: Aggregator) 
     step with neither ``max_grad_norm`` nor ``skip_nonfinite``, a process group over the library's
     communicator, and a plan psgd_plan_adam_ok serves at both parities. Like ``sgd_step_applies`` it is
     a collective on its first compressing call (it creates the library's communicator)."""
-    if type(optimizer) not in (torch.optim.Adam, torch.optim.AdamW) or type(aggregator) is not PowerSGD:
+    if not _options_served(optimizer) or type(aggregator) is not PowerSGD:
         return False
-    for g in optimizer.param_groups:
-        if g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable") or g.get("fused"):
-            return False
-        if any(torch.is_tensor(g[k]) for k in ("lr", "eps", "weight_decay")) or any(map(torch.is_tensor, g["betas"])):
-            return False
     params = params_in_optimizer(optimizer)
     dev = aggregator.device
     if not params or any(p.dtype != torch.float32 or p.device != dev or not p.is_contiguous() or p.grad is None

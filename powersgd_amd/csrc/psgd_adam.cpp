@@ -1,4 +1,4 @@
-// psgd_adam_update (include/psgd.h) and the device tables of psgd_aggregate_comm_adam's sink, as
+// psgd_adam_update / psgd_adam_update_mp (include/psgd.h) and the device tables of psgd_aggregate_comm_adam's sink, as
 // psgd_sgd.cpp keeps the SGD ones: a state of the plan's own (psgd_plan::Adam) with word tables
 // (psgd_tables.h). Pointers and work items are one table, the records another: bias correction
 // changes the records every step, so a step uploads them alone (an async copy on the codec's stream
@@ -17,8 +17,22 @@ struct psgd_plan::Adam {
     float* stage = nullptr;          // fp32 stage of the flat tail (the flat plan's layout)
     size_t stage_cap = 0;
     std::vector<void*> words;  // scratch of a call: nothing is allocated once it has its size
+    // the master-weight forms (psgd_adam_update_mp, psgd_aggregate_mixed_comm_adam): tables of their
+    // own, so a plan that mixes both forms re-binds nothing; and the ADD of the flat plan's tensors
+    // (bf16 gradients into their fp32 residual), a run table over that plan's element counts
+    WordTable mp_tab, mp_hyper, sink_w;
+    psgd_runs* unc_add = nullptr;
+    char* unc_add_ws = nullptr;
+    std::vector<int64_t> unc_add_numel;
+    void drop_unc_add() {
+        if (unc_add) (void)psgd_runs_destroy(unc_add);
+        if (unc_add_ws) (void)hipFree(unc_add_ws);
+        unc_add = nullptr;
+        unc_add_ws = nullptr;
+    }
     ~Adam() {
         if (stage) (void)hipFree(stage);
+        drop_unc_add();
     }
 };
 
@@ -85,19 +99,77 @@ int adam_select(psgd_plan* p, void* const* params, void* const* ms, void* const*
     return PSGD_OK;
 }
 
+int adam_mp_check(const psgd_plan* p, void* const* grads16, void* const* ws, const psgd_flat* f, void* const* unc16,
+                  void* const* unc_ws) {
+    const size_t nt = p->shapes.size(), nu = f ? size_t(f->count) : 0;
+    if (nu && (!unc16 || !unc_ws)) return fail(PSGD_ERR_VALUE, "null bf16 table of the flat plan's tensors");
+    for (size_t i = 0; i < nt + nu; ++i) {
+        void* const g = i < nt ? grads16[i] : unc16[i - nt];
+        void* const w = i < nt ? ws[i] : unc_ws[i - nt];
+        if (!g || !w) return fail(PSGD_ERR_VALUE, "null bf16 gradient or model parameter pointer");
+        if ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(w)) % 2)
+            return fail(PSGD_ERR_LAYOUT, "bf16 gradients and model parameters must be 2-byte aligned");
+    }
+    return PSGD_OK;
+}
+
+int adam_mp_add(psgd_plan* p, const psgd_flat* f, void* const* unc16, void* const* unc_residual, hipStream_t s) {
+    if (!f) return PSGD_OK;
+    if (!p->adam) p->adam = new psgd_plan::Adam();
+    psgd_plan::Adam& m = *p->adam;
+    const size_t nu = size_t(f->count);
+    std::vector<int64_t> numel(nu, 0);
+    for (const FlatEntry& en : f->entries) numel[size_t(en.tensor)] = en.numel;
+    if (!m.unc_add || m.unc_add_numel != numel) {
+        if (m.unc_add) PSGD_HIP(hipStreamSynchronize(s));
+        m.drop_unc_add();
+        std::vector<int64_t> zero(nu, 0);
+        std::vector<int32_t> idx(nu);
+        for (size_t i = 0; i < nu; ++i) idx[i] = int32_t(i);
+        if (int st = psgd_runs_create_mixed(zero.data(), idx.data(), zero.data(), numel.data(), idx.data(), int32_t(nu),
+                                            int32_t(nu), int32_t(nu), PSGD_BF16, PSGD_F32, &m.unc_add))
+            return st;
+        int64_t rb = 0;
+        if (int st = psgd_runs_workspace_bytes(m.unc_add, &rb)) return st;
+        PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&m.unc_add_ws), size_t(std::max<int64_t>(rb, 1))));
+        if (int st = psgd_runs_bind(m.unc_add, p->device, m.unc_add_ws)) return st;
+        m.unc_add_numel = numel;
+    }
+    return psgd_runs_add_list(m.unc_add, unc16, unc_residual, 1, s);
+}
+
+int adam_mp_select(psgd_plan* p, void* const* ws, const psgd_flat* f, void* const* unc_ws, hipStream_t s, OutSink* sink) {
+    psgd_plan::Adam& m = *p->adam;  // after adam_select
+    const size_t nt = p->shapes.size(), nu = f ? size_t(f->count) : 0;
+    std::vector<void*>& w = m.words;
+    w.clear();
+    put_ptrs(w, ws, nt);
+    put_ptrs(w, unc_ws, nu);
+    const void* tab = nullptr;
+    if (int st = m.sink_w.select(w, s, &tab)) return st;
+    void* const* t = static_cast<void* const*>(tab);
+    sink->adam_mp = true;
+    sink->ws = t;
+    sink->unc_ws = t + nt;
+    return PSGD_OK;
+}
+
 }  // namespace psgd
 
 using namespace psgd;
 
-extern "C" int psgd_adam_update(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* mo,
-                                void* const* v, const int64_t* numel, const psgd_adam_hyper* hyper, void* stream) {
-    if (!g || !p || !mo || !v || !numel || !hyper || count < 1) return fail(PSGD_ERR_VALUE, "null argument");
+// psgd_adam_update (`mp` false: w unused) and psgd_adam_update_mp (w[i] = bf16(p'[i]))
+static int adam_update_any(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* mo,
+                           void* const* v, void* const* wt, bool mp, const int64_t* numel, const psgd_adam_hyper* hyper,
+                           void* stream) {
+    if (!g || !p || !mo || !v || (mp && !wt) || !numel || !hyper || count < 1) return fail(PSGD_ERR_VALUE, "null argument");
     if (plan && !plan->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
     const size_t n = size_t(count);
     size_t nitems = 0;
     for (size_t i = 0; i < n; ++i) {
         if (!g[i] || !p[i]) return fail(PSGD_ERR_VALUE, "null tensor pointer");
         if (!mo[i] || !v[i]) return fail(PSGD_ERR_VALUE, "null moment (exp_avg / exp_avg_sq) pointer");
+        if (mp && !wt[i]) return fail(PSGD_ERR_VALUE, "null bf16 model parameter pointer");
         if (numel[i] < 0) return fail(PSGD_ERR_VALUE, "negative element count");
         nitems += size_t((numel[i] + kRunItem - 1) / kRunItem);
     }
@@ -105,6 +177,8 @@ extern "C" int psgd_adam_update(psgd_plan* plan, int32_t count, void* const* g, 
         const uintptr_t all = reinterpret_cast<uintptr_t>(g[i]) | reinterpret_cast<uintptr_t>(p[i]) |
                               reinterpret_cast<uintptr_t>(mo[i]) | reinterpret_cast<uintptr_t>(v[i]);
         if (all % 4) return fail(PSGD_ERR_LAYOUT, "averages, weights and moments must be 4-byte aligned");
+        if (mp && reinterpret_cast<uintptr_t>(wt[i]) % 2)
+            return fail(PSGD_ERR_LAYOUT, "bf16 model parameters must be 2-byte aligned");
     }
     if (nitems == 0) return PSGD_OK;
     if (nitems > size_t(INT32_MAX)) return fail(PSGD_ERR_VALUE, "too many work items");
@@ -113,9 +187,10 @@ extern "C" int psgd_adam_update(psgd_plan* plan, int32_t count, void* const* g, 
     if (plan && !plan->adam) plan->adam = new psgd_plan::Adam();
     psgd_plan::Adam& m = plan ? *plan->adam : local;
     DevScope scope(plan ? plan->device : -1);
-    // words: [g][p][m][v][items]
+    // words: [g][p][m][v][items], the master-weight form [w] ahead of them
     std::vector<void*>& w = m.words;
     w.clear();
+    if (mp) put_ptrs(w, wt, n);
     put_ptrs(w, g, n);
     put_ptrs(w, p, n);
     put_ptrs(w, mo, n);
@@ -127,12 +202,12 @@ extern "C" int psgd_adam_update(psgd_plan* plan, int32_t count, void* const* g, 
             items.push_back(SgdItem{o, int32_t(i), int32_t(std::min<int64_t>(kRunItem, numel[i] - o))});
     put(w, items.data(), items.size() * sizeof(SgdItem));
     const void* tab = nullptr;
-    if (int st = m.upd_tab.select(w, s, &tab)) return st;
+    if (int st = (mp ? m.mp_tab : m.upd_tab).select(w, s, &tab)) return st;
     w.clear();
     put(w, hyper, n * sizeof(psgd_adam_hyper));
     const void* hy = nullptr;
-    if (int st = m.upd_hyper.select(w, s, &hy)) return st;
-    void* const* t = static_cast<void* const*>(tab);
+    if (int st = (mp ? m.mp_hyper : m.upd_hyper).select(w, s, &hy)) return st;
+    void* const* t = static_cast<void* const*>(tab) + (mp ? n : 0);
     AdamArgs a{};
     a.g = t;
     a.p = t + n;
@@ -141,7 +216,19 @@ extern "C" int psgd_adam_update(psgd_plan* plan, int32_t count, void* const* g, 
     a.items = reinterpret_cast<const SgdItem*>(t + 4 * n);
     a.hyper = static_cast<const psgd_adam_hyper*>(hy);
     a.nitems = int32_t(nitems);
-    PSGD_HIP(launch_adam_update(a, s));
+    if (mp) PSGD_HIP(launch_adam_update_mp(AdamMpArgs{a, static_cast<void* const*>(tab)}, s));
+    else PSGD_HIP(launch_adam_update(a, s));
     if (!plan) PSGD_HIP(hipStreamSynchronize(s));  // `local` (tables, pinned staging) goes with the call
     return PSGD_OK;
+}
+
+extern "C" int psgd_adam_update(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* mo,
+                                void* const* v, const int64_t* numel, const psgd_adam_hyper* hyper, void* stream) {
+    return adam_update_any(plan, count, g, p, mo, v, nullptr, false, numel, hyper, stream);
+}
+
+extern "C" int psgd_adam_update_mp(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* mo,
+                                   void* const* v, void* const* w_bf16, const int64_t* numel,
+                                   const psgd_adam_hyper* hyper, void* stream) {
+    return adam_update_any(plan, count, g, p, mo, v, w_bf16, true, numel, hyper, stream);
 }

@@ -657,11 +657,13 @@ constexpr int kLowrankUR = PSGD_LOWRANK_UR;
 // kDstSgdVec / kDstSgdElem (psgd_aggregate_comm_sgd, T = float): the update forms, as in apply_tile
 // kDstAdamVec / kDstAdamElem (psgd_aggregate_comm_adam): the Adam forms; this tile caches P rows
 // only (61-129 VGPRs as an SGD form), so p, m and v all go out ahead of the row's term chain
+// kDstAdamMpVec / kDstAdamMpElem (psgd_aggregate_mixed_comm_adam): the same, and bf16(p') stored
 template <typename T, int R, int NI, int V, int DST = 0>
 __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t,
                                              const SgdTile* sg = nullptr, const AdamTile* ad = nullptr) {
     constexpr bool SGD = is_sgd_dst(DST);
     constexpr bool ADAM = is_adam_dst(DST);
+    constexpr bool MP = is_adam_mp_dst(DST);  // the master-weight forms: ad is an AdamMpTile, rW its bf16 tensor
     const TileGeom g = tile_geom<V>(d, t);
     const int r = d.r;
     T* obase;
@@ -676,6 +678,10 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
         rM = make_rsrc(ad->m + g.row_begin * g.m, uint32_t((g.row_end - g.row_begin) * g.m * 4));
         rV = make_rsrc(ad->v + g.row_begin * g.m, uint32_t((g.row_end - g.row_begin) * g.m * 4));
     }
+    rsrc_t rW = rO;
+    if constexpr (MP)
+        rW = make_rsrc(static_cast<const AdamMpTile*>(ad)->w + g.row_begin * g.m,
+                       uint32_t((g.row_end - g.row_begin) * g.m * 2));
     const int nt = NI > 0 ? NI : a.nterms;
     constexpr int NC = NI > 0 ? NI : 1;
     float ba[NC][V][R];
@@ -729,6 +735,7 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
                     else if constexpr (DST != 0 && std::is_same<T, float>::value) st_vec_dstf<DST>(rO, off, o);
                     else if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
                     else st_vec<T>(rO, off, o);
+                    if constexpr (MP) adam_mp_st<DST, V>(rW, off / 2u, pv);  // 2-byte elements
                 }
             }
         }
@@ -774,6 +781,7 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
             else if constexpr (DST != 0 && std::is_same<T, float>::value) st_vec_dstf<DST>(rO, off, o);
             else if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
             else st_vec<T>(rO, off, o);
+            if constexpr (MP) adam_mp_st<DST, V>(rW, off / 2u, pv);
         }
     }
 }

@@ -617,6 +617,25 @@ struct AdamArgs {
 };
 hipError_t launch_adam_update(const AdamArgs& a, hipStream_t s);
 
+// psgd_aggregate_mixed_comm_adam / psgd_adam_update_mp: the Adam update of fp32 master weights whose
+// bf16 model tensors take bf16(p') in the same pass. AdamDst / AdamArgs as above (p the masters) and
+// the model tensors' tables beside them: the existing kernels' argument blocks stay as they are.
+struct AdamMpDst {
+    AdamDst x;
+    void* const* ws;     // bf16 model tensors, the plan's tensor order
+    void* const* unc_w;  // the flat plan's
+};
+// psgd_adam_mp_dst.hip
+hipError_t launch_apply_adam_mp(int R, int nterms, bool shared, const ApplyArgs& a, const AdamMpDst& y, int ntiles,
+                                hipStream_t s, int* waves);
+hipError_t launch_lowrank_adam_mp(int R, int nterms, const ApplyArgs& a, const AdamMpDst& y, int ntiles, hipStream_t s,
+                                  int* waves);
+struct AdamMpArgs {
+    AdamArgs a;
+    void* const* w;
+};
+hipError_t launch_adam_update_mp(const AdamMpArgs& y, hipStream_t s);
+
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),
 // then two parities x iterations slots of xchg_slot floats each; the producer kernels (k_reduce,

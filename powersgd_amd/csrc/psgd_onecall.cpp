@@ -19,6 +19,9 @@
 //                momentum buffers at the element where it would have stored the average.
 //   fp32 adam    psgd_aggregate_comm_adam: the same with psgd_adam_update (torch's Adam / AdamW rule on
 //                the weights and both moments).
+//   bf16 master  psgd_aggregate_mixed_comm_adam: the ADD, psgd_aggregate_comm_dst on the residual into
+//                scratch destinations, psgd_adam_update_mp on them: the final pass updates the fp32
+//                master weights and moments and stores bf16(p') at the model parameters.
 // Every entry is a descriptor (Entry) and its arguments (Call): one preamble runs the checks in the
 // entry's documented order, one body makes the side state, asks admission (a refusal launches
 // nothing), builds the sink and hands it to the step driver of the entry's transport.
@@ -37,8 +40,10 @@ struct Entry {
     bool sgd = false;  // the update sink: `peer` the parameters, Call::bufs / hyper beside them; a null
                        // communicator is world size 1 without collectives
     bool adam = false;  // the Adam update sink: Call::bufs / vs the two moments, Call::adam the records
+    bool mp = false;  // adam over fp32 master weights of a bf16 model: `state` the residual, `peer` the
+                      // masters, Call::grads16 / ws the bf16 gradients and model parameters
     bool upd() const { return sgd || adam; }
-    Adm::Kind kind() const { return adam ? Adm::F32Adam : sgd ? Adm::F32Sgd : !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense; }
+    Adm::Kind kind() const { return mp ? Adm::F32AdamMp : adam ? Adm::F32Adam : sgd ? Adm::F32Sgd : !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense; }
 };
 
 // The arguments by role. `state`: the fp32 tensors the codec runs on (a bf16 sink: the residual; else
@@ -65,6 +70,11 @@ struct Call {
     void* const* vs = nullptr;
     void* const* unc_vs = nullptr;
     const psgd_adam_hyper* adam = nullptr;
+    // the master-weight sink: the bf16 gradients the ADD consumes and the bf16 model parameters
+    void* const* grads16 = nullptr;
+    void* const* unc_grads16 = nullptr;
+    void* const* ws = nullptr;
+    void* const* unc_ws = nullptr;
 };
 
 // The plans an entry serves, by shape. bf16 sinks: fp32, one bucket, rank buckets 1 / 2 / 4 (VALU
@@ -119,7 +129,8 @@ const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool
 bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
     OutSink sink;
     sink.sgd = kind == Adm::F32Sgd;
-    sink.adam = kind == Adm::F32Adam;
+    sink.adam = kind == Adm::F32Adam || kind == Adm::F32AdamMp;
+    sink.adam_mp = kind == Adm::F32AdamMp;
     sink.bf16 = kind != Adm::F32Tables && !sink.sgd && !sink.adam;
     sink.tables = kind == Adm::Bf16Tables || kind == Adm::F32Tables || sink.sgd || sink.adam;
     const int world = comm == Adm::Many ? 2 : 1;
@@ -170,6 +181,8 @@ bool eligible(psgd_plan* p, const Entry& e, int world) {
     // an update entry is defined as the destination-table step followed by psgd_sgd_update /
     // psgd_adam_update: it serves the plans whose destination instances are admitted too
     if (e.upd() && !(admitted(p, Adm::F32Tables, Adm::Many) && admitted(p, Adm::F32Tables, Adm::One))) return false;
+    // the master-weight entry applies psgd_plan_adam_ok's rule, then asks for its own instances
+    if (e.mp && !(admitted(p, Adm::F32Adam, Adm::Many) && admitted(p, Adm::F32Adam, Adm::One))) return false;
     if (e.wide || !e.bf16) return admitted(p, e.kind(), Adm::Many) && admitted(p, e.kind(), Adm::One);
     return admitted(p, e.kind(), world == 1 ? Adm::One : Adm::Many);
 }
@@ -232,7 +245,7 @@ void release(psgd_plan::Side*& slot) {
 int preamble(const Entry& e, Call& c) {
     const psgd_plan* p = c.p;
     const bool args = p && c.state && c.peer && (e.tables || c.out) && (e.via != Entry::Comm || c.comm || e.upd()) &&
-                      (!e.sgd || c.hyper) && (!e.adam || (c.bufs && c.vs && c.adam));
+                      (!e.sgd || c.hyper) && (!e.adam || (c.bufs && c.vs && c.adam)) && (!e.mp || (c.grads16 && c.ws));
     if (e.via == Entry::Xchg) {
         if (!args) return fail(PSGD_ERR_VALUE, "null argument");
         if (c.step < 0) return fail(PSGD_ERR_VALUE, "step out of range");
@@ -278,6 +291,8 @@ int preamble(const Entry& e, Call& c) {
         if (int st = sgd_check(p, c.bufs, c.f, c.unc_bufs, c.hyper)) return st;
     if (e.adam)
         if (int st = adam_check(p, c.bufs, c.vs, c.f, c.unc_bufs, c.unc_vs)) return st;
+    if (e.mp)
+        if (int st = adam_mp_check(p, c.grads16, c.ws, c.f, c.unc_grads16, c.unc_ws)) return st;
     if (e.via == Entry::Xchg) {
         if (int st = ipc_check(p, c.step)) return st;
         if (c.f && c.f->total > p->ipc_flat_cap)
@@ -305,6 +320,12 @@ int body(const Entry& e, const Call& c, bool* refused) {
         if (e.adam) {
             if (int st = adam_select(p, c.peer, c.bufs, c.vs, f, c.unc_peer, c.unc_bufs, c.unc_vs, c.adam, s, &sink))
                 return st;
+            if (e.mp) {  // the model tensors' tables; then the ADD over every tensor, the first launches
+                if (int st = adam_mp_select(p, c.ws, f, c.unc_ws, s, &sink)) return st;
+                if (int st = ensure(p, p->mixed, true)) return st;
+                if (int st = psgd_runs_add_list(p->mixed->add, c.grads16, c.state, 1, s)) return st;
+                if (int st = adam_mp_add(p, f, c.unc_grads16, c.unc_state, s)) return st;
+            }
         } else if (int st = sgd_select(p, c.peer, c.bufs, f, c.unc_peer, c.unc_bufs, c.hyper, s, &sink)) {
             return st;
         }
@@ -395,6 +416,7 @@ const Entry kCommDst{"psgd_aggregate_comm_dst", Entry::Comm, false, true, false}
 const Entry kIpcDst{"psgd_aggregate_ipc_dst", Entry::Xchg, false, true, false};
 const Entry kCommSgd{"psgd_aggregate_comm_sgd", Entry::Comm, false, true, false, true};
 const Entry kCommAdam{"psgd_aggregate_comm_adam", Entry::Comm, false, true, false, false, true};
+const Entry kMixedCommAdam{"psgd_aggregate_mixed_comm_adam", Entry::Comm, false, true, false, false, true, true};
 
 }  // namespace
 
@@ -512,6 +534,32 @@ int psgd_aggregate_comm_adam(psgd_plan* p, void* const* grads, void* const* para
     c.unc_vs = unc_vs;
     c.adam = hyper;
     return run(kCommAdam, c);
+}
+
+int psgd_plan_mixed_adam_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, false, false, &code, false, true)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kMixedCommAdam, world) ? 1 : 0; });
+}
+
+int psgd_aggregate_mixed_comm_adam(psgd_plan* p, void* const* grads_bf16, void* const* residual,
+                                   void* const* params_bf16, void* const* masters, void* const* ms, void* const* vs,
+                                   const psgd_adam_hyper* hyper, int64_t step, psgd_flat* f, void* const* unc_bf16,
+                                   void* const* unc_residual, void* const* unc_params_bf16, void* const* unc_masters,
+                                   void* const* unc_ms, void* const* unc_vs, psgd_comm* comm, void* stream) {
+    Call c{p, residual, masters, nullptr, step, f, unc_residual, unc_masters, nullptr, comm, stream};
+    c.bufs = ms;
+    c.unc_bufs = unc_ms;
+    c.vs = vs;
+    c.unc_vs = unc_vs;
+    c.adam = hyper;
+    c.grads16 = grads_bf16;
+    c.unc_grads16 = unc_bf16;
+    c.ws = params_bf16;
+    c.unc_ws = unc_params_bf16;
+    return run(kMixedCommAdam, c);
 }
 
 int psgd_aggregate_mixed_flat(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,

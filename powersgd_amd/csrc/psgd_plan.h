@@ -420,7 +420,8 @@ struct psgd_plan {
         enum Kind {
             Bf16Dense, Bf16Tables, F32Tables, Bf16Ingest /* world size 1, the single-pass final kernel */,
             F32Sgd /* the update instances of psgd_aggregate_comm_sgd */,
-            F32Adam /* the Adam instances of psgd_aggregate_comm_adam */, kKinds
+            F32Adam /* the Adam instances of psgd_aggregate_comm_adam */,
+            F32AdamMp /* the master-weight instances of psgd_aggregate_mixed_comm_adam */, kKinds
         };
         enum Comm { NoComm /* aggregate_ctx */, Many /* world size > 1 */, One /* a 1-rank communicator */, kComms };
         uint64_t key = ~uint64_t(0);
@@ -613,6 +614,12 @@ struct OutSink {
     void* const* unc_vs = nullptr;
     const psgd_adam_hyper* adam_hyper = nullptr;
     AdamDst adam_dst() const { return AdamDst{bufs, vs, unc_dst, unc_bufs, unc_vs, stage, adam_hyper, hyper_unc0}; }
+    // psgd_aggregate_mixed_comm_adam: `adam` with `dst` / `unc_dst` the fp32 master weights, and the
+    // bf16 model tensors that take bf16(p') in the same pass
+    bool adam_mp = false;
+    void* const* ws = nullptr;
+    void* const* unc_ws = nullptr;
+    AdamMpDst adam_mp_dst() const { return AdamMpDst{adam_dst(), ws, unc_ws}; }
     // the flat tail's bf16 gradients are added in the step, (x + float(g)) / W in a launch of its
     // own ahead of every collective; else the tail is packed as psgd_aggregate_comm packs it
     bool ingests() const { return bf16 && !tables; }
@@ -773,6 +780,14 @@ int adam_check(const psgd_plan* p, void* const* ms, void* const* vs, const psgd_
 int adam_select(psgd_plan* p, void* const* params, void* const* ms, void* const* vs, const psgd_flat* f,
                 void* const* unc_params, void* const* unc_ms, void* const* unc_vs, const psgd_adam_hyper* hyper,
                 hipStream_t s, OutSink* sink);
+// psgd_aggregate_mixed_comm_adam: the bf16 side. adam_mp_check: the model tensors and the bf16
+// gradients (null: PSGD_ERR_VALUE; not 2-byte aligned: PSGD_ERR_LAYOUT). adam_mp_add: the ADD of the
+// flat plan's tensors (residual += float(g); g = +0.0), a run table of the Adam state's own made at
+// the first call. adam_mp_select: after adam_select, the model tensors' tables into the sink.
+int adam_mp_check(const psgd_plan* p, void* const* grads16, void* const* ws, const psgd_flat* f, void* const* unc16,
+                  void* const* unc_ws);
+int adam_mp_add(psgd_plan* p, const psgd_flat* f, void* const* unc16, void* const* unc_residual, hipStream_t s);
+int adam_mp_select(psgd_plan* p, void* const* ws, const psgd_flat* f, void* const* unc_ws, hipStream_t s, OutSink* sink);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
 int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
 // The world-size-W step into `sink`: over a communicator (psgd_step.cpp; `comm` null: world size 1,

@@ -538,6 +538,10 @@ hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArg
         if (sink->sgd)  // the update applied where the average would have been stored
             return o.kind == OutRoute::Lowrank ? launch_lowrank_sgd(R, I, a, sink->sgd_dst(), ntiles, s, waves)
                                                : launch_apply_sgd(R, I, o.shared, a, sink->sgd_dst(), ntiles, s, waves);
+        if (sink->adam_mp)  // the Adam update of master weights, bf16(p') stored at the model tensors
+            return o.kind == OutRoute::Lowrank
+                       ? launch_lowrank_adam_mp(R, I, a, sink->adam_mp_dst(), ntiles, s, waves)
+                       : launch_apply_adam_mp(R, I, o.shared, a, sink->adam_mp_dst(), ntiles, s, waves);
         if (sink->adam)  // the Adam update likewise
             return o.kind == OutRoute::Lowrank ? launch_lowrank_adam(R, I, a, sink->adam_dst(), ntiles, s, waves)
                                                : launch_apply_adam(R, I, o.shared, a, sink->adam_dst(), ntiles, s, waves);

@@ -335,11 +335,22 @@ constexpr bool is_sgd_dst(int dst) { return dst == kDstSgdVec || dst == kDstSgdE
 // shared by p, m and v and formed again at the store. The record is read once per tile from
 // workgroup-uniform addresses; the decay branch and the lerp side are scalar.
 constexpr int kDstAdamVec = 5, kDstAdamElem = 6;
-constexpr bool is_adam_dst(int dst) { return dst == kDstAdamVec || dst == kDstAdamElem; }
+// The master-weight forms (psgd_aggregate_mixed_comm_adam, psgd_adam_mp_dst.hip): the Adam forms on
+// the fp32 master weight and moments, and the new weight rounded to bf16 (round to nearest even,
+// bf16_pin_t) stored at the model parameter's own address through a fourth descriptor: the tile's
+// rows of the model tensor in 2-byte elements. kDstAdamMpVec: the tile's first element is 16-byte
+// aligned in p, m and v and 8-byte aligned in w (one 8-byte store per row quad); kDstAdamMpElem:
+// 4-byte accesses of p, m, v and four 2-byte stores of w.
+constexpr int kDstAdamMpVec = 7, kDstAdamMpElem = 8;
+constexpr bool is_adam_mp_dst(int dst) { return dst == kDstAdamMpVec || dst == kDstAdamMpElem; }
+constexpr bool is_adam_dst(int dst) { return dst == kDstAdamVec || dst == kDstAdamElem || is_adam_mp_dst(dst); }
 struct AdamTile {
     float* m;  // the tensor's exp_avg and exp_avg_sq
     float* v;
     psgd_adam_hyper h;
+};
+struct AdamMpTile : AdamTile {
+    uint16_t* w;  // the bf16 model tensor of the master weight a.odst names
 };
 // The only place the formula is written. Every product is a rounded fp32 value of its own
 // (mul_rn), sqrt and the divisions are the correctly rounded ones of the default build
@@ -377,7 +388,7 @@ constexpr int adam_rows_in_flight(int R, int NI, bool shared) {
 }
 template <int DST>
 __device__ __forceinline__ constexpr int adam_io() {  // the load / store form of the same width
-    return DST == kDstAdamElem ? kDstSgdElem : kDstSgdVec;
+    return DST == kDstAdamElem || DST == kDstAdamMpElem ? kDstSgdElem : kDstSgdVec;
 }
 // The epilogue: the averages pinned as sgd_apply pins them (the destination instance's store
 // form), THE UPDATE on the loaded p / m / v, three plain stores
@@ -401,6 +412,15 @@ __device__ __forceinline__ void adam_apply(const AdamTile& ad, rsrc_t rP, rsrc_t
     sgd_st<adam_io<DST>()>(rP, off, pv);
     sgd_st<adam_io<DST>()>(rM, off, mv);
     sgd_st<adam_io<DST>()>(rV, off, vv);
+}
+// the master-weight forms' fourth store: bf16(p') of the values adam_apply has just stored, at byte
+// offset `woff` of the model tensor's descriptor (2-byte elements; kOob: dropped). Plain stores: the
+// next forward pass reads them
+template <int DST, int V>
+__device__ __forceinline__ void adam_mp_st(rsrc_t rW, uint32_t woff, const float (&pv)[V]) {
+    if constexpr (V == 1) StIo<bf16_pin_t>::template st1<0>(rW, woff, pv[0]);
+    else if constexpr (DST == kDstAdamMpElem) StIo<bf16_pin_t>::template st4e<0>(rW, woff, pv);
+    else StIo<bf16_pin_t>::template st4<0>(rW, woff, pv);
 }
 
 template <typename T>
@@ -1390,6 +1410,7 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
                                            const SgdTile* sg = nullptr, const AdamTile* ad = nullptr) {
     constexpr bool SGD = is_sgd_dst(DST);  // the update forms: rO spans the tile's rows of p, rB of buf
     constexpr bool ADAM = is_adam_dst(DST);  // rO spans p, rM / rV the two moments
+    constexpr bool MP = is_adam_mp_dst(DST);  // rW the bf16 model tensor (ad is an AdamMpTile)
     // rows in flight per lane. The update forms of the two-set instances that cache 12 or more
     // factor columns per set keep 2: their destination twins sit at the register edge with 4
     // (k_apply_dst<4, 3, false>: 255 VGPRs), and p, buf and the update's temporaries do not fit
@@ -1416,6 +1437,10 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
         rM = make_rsrc(ad->m + g.row_begin * g.m, tb);
         rV = make_rsrc(ad->v + g.row_begin * g.m, tb);
     }
+    rsrc_t rW = rO;
+    if constexpr (MP)
+        rW = make_rsrc(static_cast<const AdamMpTile*>(ad)->w + g.row_begin * g.m,
+                       uint32_t((g.row_end - g.row_begin) * g.m * 2));
     const int nt = NI > 0 ? NI : a.nterms;
     constexpr int NC = NI > 0 ? NI : 1;
     constexpr int NA = (NI > 0 && !SHARED) ? NI : 1;
@@ -1531,6 +1556,7 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
                     if constexpr (kAdamAhead < 2) sgd_ld<adam_io<DST>()>(rM, eo * 4u, bv);
                     if constexpr (kAdamAhead < 3) sgd_ld<adam_io<DST>()>(rV, eo * 4u, vv);
                     adam_apply<DST, V>(*ad, rO, rM, rV, eo * 4u, o, pv, bv, vv);
+                    if constexpr (MP) adam_mp_st<DST, V>(rW, eo * 2u, pv);
                 } else if constexpr (DST != 0 && std::is_same<TO, float>::value)
                     st_vec_dstf<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, eo * uint32_t(sizeof(TO)), o);
                 else if constexpr (DST != 0)
@@ -1579,6 +1605,7 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
                                                 const SgdTile* sg = nullptr, const AdamTile* ad = nullptr) {
     constexpr bool SGD = is_sgd_dst(DST);  // the update forms (T = TO = float): rO spans p, rB buf
     constexpr bool ADAM = is_adam_dst(DST);  // rO spans p, rM / rV the two moments
+    constexpr bool MP = is_adam_mp_dst(DST);  // rW the bf16 model tensor (ad is an AdamMpTile)
     constexpr int KQ = R / 4;
     constexpr int RP = ApplyMfmaLds<R>::RP;
     constexpr int NS = SHARED ? 1 : 2;
@@ -1632,6 +1659,10 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
         rM = make_rsrc(ad->m + row_begin * m, tb);
         rV = make_rsrc(ad->v + row_begin * m, tb);
     }
+    rsrc_t rW = rO;
+    if constexpr (MP)
+        rW = make_rsrc(static_cast<const AdamMpTile*>(ad)->w + row_begin * m,
+                       uint32_t((row_end - row_begin) * int64_t(m) * 2));
     const uint32_t cofs = active ? uint32_t(col) * s : kOob;
     const uint32_t rstride = uint32_t(m) * s;
     const bool pvec = r == R && (d.poff & 3) == 0;
@@ -1732,6 +1763,12 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
                 if constexpr (kAdamAheadMfma < 2) sgd_ld<adam_io<DST>()>(rM, off, bv[v]);
                 if constexpr (kAdamAheadMfma < 3) sgd_ld<adam_io<DST>()>(rV, off, vv[v]);
                 adam_apply<DST, 4>(*ad, rO, rM, rV, off, oo, pv[v], bv[v], vv[v]);
+                if constexpr (MP) {
+                    // in 2-byte elements: in range or kOob, by the explicit test (the bf16 tile's
+                    // rule above)
+                    const bool in = active && b0 + 4 * cq + v < row_end;
+                    adam_mp_st<DST, 4>(rW, in ? ((rb + v) * uint32_t(m) + uint32_t(col)) * 2u : kOob, pv[v]);
+                }
             } else if constexpr (DST != 0) {
                 st_vec_dstf<DST, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, off, oo);
             } else {

@@ -166,6 +166,16 @@ class Fp32ResidualPowerSGD(Aggregator, metaclass=_ClipKeyword):
         self._gather.gather(self._slab.data_ptr(), ctypes.addressof(self._out_ptrs), stream)
         return outs
 
+    def aggregate_fp32(self, gradients: List[torch.Tensor]) -> List[torch.Tensor]:
+        """``aggregate`` without its last stage: the ADD and ``inner.aggregate(views)``, returning the
+        unrounded fp32 averages (for an optimizer that runs on fp32 master weights,
+        ``adam_master_step``). The gradients are zeroed as in ``aggregate``."""
+        if not isinstance(gradients, list):
+            gradients = list(gradients)
+        self._table.fill(gradients)
+        self._add.add_list(self._table.comp_addr(), ctypes.addressof(self._res_ptrs), True, _stream(self.device))
+        return self.inner.aggregate(self.views)
+
     def _fused_comm(self):
         """The library's own communicator when this process group runs over it (``PowerSGD.aggregate``'s
         choice: RCCL, not ``PSGD_COMM=ipc`` / ``torch``, not gloo), else None. Collective on first use."""

@@ -832,6 +832,48 @@ int psgd_aggregate_mixed_comm_adam(psgd_plan* plan, void* const* grads_bf16, voi
                                    void* const* unc_ms, void* const* unc_vs, psgd_comm* comm, void* stream);
 int psgd_plan_mixed_adam_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
 
+/* ------- the fused Adam / AdamW steps at ranks 33-128 (a wide plan, psgd_plan_is_wide) ------- */
+/* psgd_aggregate_comm_adam_wide: psgd_aggregate_comm_adam's arguments on a wide plan, which that
+ * entry refuses. A wide plan has no destination-table step, so this one is DEFINED against the slab
+ * and equal to it bit for bit (every p, m, v, residual, P/Q state; the same collectives):
+ *   1. psgd_aggregate_comm(plan, grads, out, step, flat, unc, flat_out, comm) into scratch slabs
+ *   2. psgd_adam_update on those averages with params / ms / vs (then unc_params / unc_ms / unc_vs)
+ * Where it runs: the final pass as k_wide_apply_adam (psgd_wide_adam.hip): k_wide_apply<float>'s
+ * tile and MFMA sequence with the factor blocks staged in LDS (psgd_aggregate_mixed_wide's pass), so
+ * the residual and the average g of an element have k_wide_apply's bits; at the element where g
+ * would have been stored, p, m and v are read from the tensor's own buffers, take THE UPDATE and
+ * are stored back. A tile takes 16-byte accesses where m % 4 == 0 and p, m and v are 16-byte
+ * aligned, else 4-byte ones, chosen once per tile; every access is predicated on its own row and
+ * column, nothing outside the numel elements of a tensor is read or written. The flat tail is
+ * packed in a launch of its own, summed by the last collective into the plan's stage, and updated
+ * by the leading workgroups of the final launch. `comm` NULL: world size 1, no collectives.
+ * Eligible: an fp32 wide plan of one bucket whose instance for the communicator kind asked (one
+ * rank: shared terms; else two term sets) is admitted (two waves per SIMD, no scratch; asked once
+ * per plan). psgd_plan_adam_wide_ok: *ok = 1 for such a plan at `world`. A refusal launches nothing
+ * and issues no collective.
+ * Refusals: psgd_aggregate_comm_adam's codes in its order; a plan that is not wide: PSGD_ERR_VALUE. */
+int psgd_aggregate_comm_adam_wide(psgd_plan* plan, void* const* grads, void* const* params, void* const* ms,
+                                  void* const* vs, const psgd_adam_hyper* hyper, int64_t step, psgd_flat* flat,
+                                  void* const* unc, void* const* unc_params, void* const* unc_ms,
+                                  void* const* unc_vs, psgd_comm* comm, void* stream);
+int psgd_plan_adam_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
+
+/* psgd_aggregate_mixed_comm_adam_wide: psgd_aggregate_mixed_comm_adam's arguments on a wide plan.
+ * DEFINED as, and bit for bit equal to: the ADD over every tensor (residual += float(g); g = +0.0),
+ * psgd_aggregate_comm on the residual into scratch slabs, psgd_adam_update_mp on those averages. The
+ * ADD's launches are psgd_aggregate_mixed_comm_adam's; the final pass is the master-weight form of
+ * k_wide_apply_adam, which also stores bf16(p') (round to nearest even of the stored fp32 p') at
+ * the model tensor: 8 bytes per row quad where m % 4 == 0 and the tensor is 8-byte aligned, else
+ * 2-byte stores. Eligibility, the query and the refusals as above (psgd_aggregate_mixed_comm_adam's
+ * codes). */
+int psgd_aggregate_mixed_comm_adam_wide(psgd_plan* plan, void* const* grads_bf16, void* const* residual,
+                                        void* const* params_bf16, void* const* masters, void* const* ms,
+                                        void* const* vs, const psgd_adam_hyper* hyper, int64_t step,
+                                        psgd_flat* flat, void* const* unc_bf16, void* const* unc_residual,
+                                        void* const* unc_params_bf16, void* const* unc_masters, void* const* unc_ms,
+                                        void* const* unc_vs, psgd_comm* comm, void* stream);
+int psgd_plan_mixed_adam_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
+
 /* ------------------------ global-norm clipping of a step's averages (clip_grad_norm_) ---------- */
 /* torch.nn.utils.clip_grad_norm_ (L2) over everything a step returned, on the stream, with no host
  * synchronisation: norm = sqrt(sum of squares of the compressed averages `out` and of the dense

@@ -109,6 +109,10 @@ _SIGNATURES = {
     "psgd_adam_update_mp": ([_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_aggregate_mixed_comm_adam": ([_vp] * 8 + [_i64] + [_vp] * 9, _i32),
     "psgd_plan_mixed_adam_ok": ([_vp, _i64, _i32, _P_i32], _i32),
+    "psgd_aggregate_comm_adam_wide": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_adam_wide_ok": ([_vp, _i64, _i32, _P_i32], _i32),
+    "psgd_aggregate_mixed_comm_adam_wide": ([_vp] * 8 + [_i64] + [_vp] * 9, _i32),
+    "psgd_plan_mixed_adam_wide_ok": ([_vp, _i64, _i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -418,13 +422,23 @@ class Plan:
         return int(ok.value)
 
     def aggregate_comm_adam(self, grads, params, ms, vs, hyper, step: int, comm: Optional["Comm"], stream: int,
-                            flat=None, unc=None, unc_params=None, unc_ms=None, unc_vs=None) -> None:
+                            flat=None, unc=None, unc_params=None, unc_ms=None, unc_vs=None, wide: bool = False) -> None:
         """psgd_aggregate_comm_adam: ``aggregate_comm_dst`` followed by ``adam_update`` in one call; the final
         pass updates ``params[i]`` / ``ms[i]`` / ``vs[i]`` (then the flat plan's) and stores no average.
-        ``hyper``: ``adam_hyper`` records, the plan's tensors then the flat plan's."""
-        check(lib().psgd_aggregate_comm_adam(self._h, grads, params, ms, vs, ctypes.addressof(hyper) if hyper is not None
-                                             else None, step, flat._h if flat is not None else None, unc, unc_params,
-                                             unc_ms, unc_vs, comm._h if comm is not None else None, stream))
+        ``hyper``: ``adam_hyper`` records, the plan's tensors then the flat plan's. ``wide``:
+        psgd_aggregate_comm_adam_wide, the same on a plan of ranks 33-128 (``aggregate_comm`` followed by
+        ``adam_update``)."""
+        fn = lib().psgd_aggregate_comm_adam_wide if wide else lib().psgd_aggregate_comm_adam
+        check(fn(self._h, grads, params, ms, vs, ctypes.addressof(hyper) if hyper is not None else None, step,
+                 flat._h if flat is not None else None, unc, unc_params, unc_ms, unc_vs,
+                 comm._h if comm is not None else None, stream))
+
+    def adam_wide_ok(self, step: int, world: int) -> int:
+        """1 where ``aggregate_comm_adam(wide=True)`` serves this plan at ``world`` (psgd_plan_adam_wide_ok: an
+        fp32 wide plan of one bucket whose k_wide_apply_adam instance is admitted)."""
+        ok = _i32()
+        check(lib().psgd_plan_adam_wide_ok(self._h, step, world, ctypes.byref(ok)))
+        return int(ok.value)
 
     # --- the fused Adam / AdamW step of a bf16 model with fp32 master weights
     def mixed_adam_ok(self, step: int, world: int) -> int:
@@ -434,17 +448,25 @@ class Plan:
         check(lib().psgd_plan_mixed_adam_ok(self._h, step, world, ctypes.byref(ok)))
         return int(ok.value)
 
+    def mixed_adam_wide_ok(self, step: int, world: int) -> int:
+        """``adam_wide_ok`` for the master-weight form (psgd_plan_mixed_adam_wide_ok)."""
+        ok = _i32()
+        check(lib().psgd_plan_mixed_adam_wide_ok(self._h, step, world, ctypes.byref(ok)))
+        return int(ok.value)
+
     def aggregate_mixed_comm_adam(self, grads_bf16, residual, params_bf16, masters, ms, vs, hyper, step: int,
                                   comm: Optional["Comm"], stream: int, flat=None, unc_bf16=None, unc_residual=None,
-                                  unc_params_bf16=None, unc_masters=None, unc_ms=None, unc_vs=None) -> None:
+                                  unc_params_bf16=None, unc_masters=None, unc_ms=None, unc_vs=None,
+                                  wide: bool = False) -> None:
         """psgd_aggregate_mixed_comm_adam: the ADD of the bf16 gradients into ``residual``,
         ``aggregate_comm_dst`` on it and ``adam_update_mp`` in one call: the final pass updates
-        ``masters[i]`` / ``ms[i]`` / ``vs[i]`` and stores ``params_bf16[i] = bf16(masters[i])``."""
-        check(lib().psgd_aggregate_mixed_comm_adam(
-            self._h, grads_bf16, residual, params_bf16, masters, ms, vs,
-            ctypes.addressof(hyper) if hyper is not None else None, step, flat._h if flat is not None else None,
-            unc_bf16, unc_residual, unc_params_bf16, unc_masters, unc_ms, unc_vs,
-            comm._h if comm is not None else None, stream))
+        ``masters[i]`` / ``ms[i]`` / ``vs[i]`` and stores ``params_bf16[i] = bf16(masters[i])``. ``wide``:
+        psgd_aggregate_mixed_comm_adam_wide, the same on a plan of ranks 33-128."""
+        fn = lib().psgd_aggregate_mixed_comm_adam_wide if wide else lib().psgd_aggregate_mixed_comm_adam
+        check(fn(self._h, grads_bf16, residual, params_bf16, masters, ms, vs,
+                 ctypes.addressof(hyper) if hyper is not None else None, step, flat._h if flat is not None else None,
+                 unc_bf16, unc_residual, unc_params_bf16, unc_masters, unc_ms, unc_vs,
+                 comm._h if comm is not None else None, stream))
 
     def aggregate_ipc_dst(self, grads, dst, step: int, stream: int, flat=None, unc=None, unc_dst=None) -> None:
         """psgd_aggregate_ipc_dst: the same over the plan's open exchange session (``aggregate_ipc``)."""

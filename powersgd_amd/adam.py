@@ -47,7 +47,7 @@ def adam_step_applies(optimizer: torch.optim.Optimizer, aggregator: Aggregator) 
     ``amsgrad``, ``maximize``, ``capturable`` and ``differentiable`` off and ``fused`` not on, fp32
     contiguous parameters on the aggregator's device with gradients, a ``PowerSGD`` on a compressing
     step with neither ``max_grad_norm`` nor ``skip_nonfinite``, a process group over the library's
-    communicator, and a plan psgd_plan_adam_ok serves at both parities. Like ``sgd_step_applies`` it is
+    communicator, and a plan psgd_plan_adam_ok (ranks 33-128: psgd_plan_adam_wide_ok) serves at both parities. Like ``sgd_step_applies`` it is
     a collective on its first compressing call (it creates the library's communicator)."""
     if not _options_served(optimizer) or type(aggregator) is not PowerSGD:
         return False
@@ -66,7 +66,8 @@ def adam_step_applies(optimizer: torch.optim.Optimizer, aggregator: Aggregator) 
     if comm is None:
         return False
     plan = aggregator._powersgd._plan
-    return plan.adam_ok(0, comm.world) == 1 and plan.adam_ok(1, comm.world) == 1
+    ok = plan.adam_wide_ok if plan.is_wide() else plan.adam_ok  # ranks 33-128: psgd_aggregate_comm_adam_wide
+    return ok(0, comm.world) == 1 and ok(1, comm.world) == 1
 
 
 def _records(optimizer: torch.optim.Optimizer, params: List[torch.Tensor]):
@@ -121,5 +122,6 @@ def adam_step(optimizer: torch.optim.Optimizer, aggregator: Aggregator) -> None:
         kw = dict(flat=aggregator._unc.plan, unc=aggregator._table.unc_addr(), unc_params=ptab.unc_addr(),
                   unc_ms=mtab.unc_addr(), unc_vs=vtab.unc_addr())
     codec._plan.aggregate_comm_adam(aggregator._table.comp_addr(), ptab.comp_addr(), mtab.comp_addr(), vtab.comp_addr(),
-                                    hyper, codec.step_counter, comm, _stream(aggregator.device), **kw)
+                                    hyper, codec.step_counter, comm, _stream(aggregator.device),
+                                    wide=codec._plan.is_wide(), **kw)
     codec.step_counter += 1

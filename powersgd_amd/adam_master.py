@@ -48,7 +48,7 @@ def adam_master_step_applies(optimizer: torch.optim.Optimizer, aggregator: Fp32R
     option rules over fp32 contiguous masters, an ``Fp32ResidualPowerSGD`` over the bf16 contiguous
     ``model_params`` (with gradients) on its device, a compressing step with neither ``max_grad_norm``
     nor ``skip_nonfinite``, a process group over the library's communicator, and a plan
-    psgd_plan_mixed_adam_ok serves at both parities. A collective on its first compressing call (it
+    psgd_plan_mixed_adam_ok (ranks 33-128: psgd_plan_mixed_adam_wide_ok) serves at both parities. A collective on its first compressing call (it
     creates the library's communicator)."""
     if not _options_served(optimizer) or type(aggregator) is not Fp32ResidualPowerSGD:
         return False
@@ -69,7 +69,8 @@ def adam_master_step_applies(optimizer: torch.optim.Optimizer, aggregator: Fp32R
     if comm is None:
         return False
     plan = aggregator.inner._powersgd._plan
-    return plan.mixed_adam_ok(0, comm.world) == 1 and plan.mixed_adam_ok(1, comm.world) == 1
+    ok = plan.mixed_adam_wide_ok if plan.is_wide() else plan.mixed_adam_ok  # ranks 33-128: the wide entry
+    return ok(0, comm.world) == 1 and ok(1, comm.world) == 1
 
 
 def _unfused(optimizer, aggregator, masters: List[torch.Tensor], model: List[torch.Tensor]) -> None:
@@ -119,5 +120,5 @@ def adam_master_step(optimizer: torch.optim.Optimizer, aggregator: Fp32ResidualP
                   unc_vs=vtab.unc_addr())
     codec._plan.aggregate_mixed_comm_adam(gtab.comp_addr(), inner._table.comp_addr(), wtab.comp_addr(), ptab.comp_addr(),
                                           mtab.comp_addr(), vtab.comp_addr(), hyper, codec.step_counter, comm,
-                                          _stream(aggregator.device), **kw)
+                                          _stream(aggregator.device), wide=codec._plan.is_wide(), **kw)
     codec.step_counter += 1

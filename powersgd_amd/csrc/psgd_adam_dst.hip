@@ -16,6 +16,7 @@
 // ahead of the MFMA chain (matrix-core tiles); the VALU instances that cache their factor columns
 // keep two rows in flight per lane instead of four where four would leave two waves per SIMD
 // (adam_rows_in_flight).
+#include "psgd_adam_flat.cuh"  // flat_adam_item: the flat tail's update items
 #include "psgd_final.cuh"
 
 namespace psgd {
@@ -37,48 +38,6 @@ __device__ __forceinline__ bool adam_al16(const ApplyArgs& a, const AdamTile& ad
     const uintptr_t m = reinterpret_cast<uintptr_t>(ad.m) + o;
     const uintptr_t v = reinterpret_cast<uintptr_t>(ad.v) + o;
     return ((p | m | v) & 15) == 0;
-}
-
-// Update item of the flat tail: g is the item's elements of the all-reduced stage (the flat plan's
-// layout), p / m / v the tensor's own (4-byte aligned: element accesses). flat_sgd_item's shape: the
-// descriptors span the item's elements of that tensor alone, every load is issued before the
-// first store.
-template <int NT>
-__device__ __forceinline__ void flat_adam_item(const FlatArgs& a, const AdamDst& x, int item) {
-    constexpr int PER = kFlatItem / NT;
-    const FlatItem it = a.items[item];
-    const FlatEntry en = a.entries[it.entry];
-    const psgd_adam_hyper h = x.hyper[x.unc0 + en.tensor];
-    const gptr<const float> st = gconst<float>(x.stage) + en.off;
-    const uint32_t cnt = uint32_t(en.numel - it.start < kFlatItem ? en.numel - it.start : kFlatItem);
-    const rsrc_t rP = make_rsrc(static_cast<float*>(x.unc_p[en.tensor]) + it.start, cnt * 4u);
-    const rsrc_t rM = make_rsrc(static_cast<float*>(x.unc_m[en.tensor]) + it.start, cnt * 4u);
-    const rsrc_t rV = make_rsrc(static_cast<float*>(x.unc_v[en.tensor]) + it.start, cnt * 4u);
-    float g[PER], p[PER], m[PER], v[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int64_t j = it.start + int64_t(q) * NT + threadIdx.x;
-        const uint32_t off = uint32_t(int64_t(q) * NT + threadIdx.x) * 4u;
-        g[q] = st[j < en.numel ? j : 0];  // clamped, unconditional
-        p[q] = BufIo<float>::ld1(rP, off);  // past the item: zeros, no access
-        m[q] = BufIo<float>::ld1(rM, off);
-        v[q] = BufIo<float>::ld1(rV, off);
-    }
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        keep(g[q]);
-        keep(p[q]);
-        keep(m[q]);
-        keep(v[q]);
-    }
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t off = uint32_t(int64_t(q) * NT + threadIdx.x) * 4u;
-        adam_update(h, g[q], p[q], m[q], v[q]);
-        StIo<float>::st1<0>(rP, off, p[q]);  // past the item: dropped by the descriptor
-        StIo<float>::st1<0>(rM, off, m[q]);
-        StIo<float>::st1<0>(rV, off, v[q]);
-    }
 }
 
 // k_apply_dst<R, NI, SHARED, false> with the Adam forms; the flat tail's update items lead

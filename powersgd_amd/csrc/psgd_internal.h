@@ -636,6 +636,23 @@ struct AdamMpArgs {
 };
 hipError_t launch_adam_update_mp(const AdamMpArgs& y, hipStream_t s);
 
+// psgd_aggregate_comm_adam_wide / psgd_aggregate_mixed_comm_adam_wide (ranks 33-128): k_wide_apply_mix's
+// LDS-staged pass (WideArgs as for launch_wide_apply_mix; a.out unused) whose epilogue applies THE
+// UPDATE at the element where k_wide_apply<float> would have stored the fp32 average. WideArgs has
+// neither a destination table nor flat items, so both come in this second kernel argument: `p` the
+// parameters (master weights) in the plan's tensor order, `y` the moments, records, the flat plan's
+// tables and the staged flat tail (y.ws / y.unc_w: the master-weight form's bf16 model tensors, else
+// unused), `flat` the flat tail's update items, which lead the launch.
+struct WideAdamDst {
+    void* const* p;
+    AdamMpDst y;
+    FlatArgs flat;
+};
+// psgd_wide_adam.hip. `mp`: the master-weight form. ntiles + items == 0: no launch; `*waves` (if
+// non-null) receives the resident waves per SIMD of the instance that would run, 0 with scratch.
+hipError_t launch_wide_apply_adam(int R, bool mp, const WideArgs& a, const WideAdamDst& x, int ntiles, hipStream_t s,
+                                  int* waves);
+
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),
 // then two parities x iterations slots of xchg_slot floats each; the producer kernels (k_reduce,

@@ -22,6 +22,9 @@
 //   bf16 master  psgd_aggregate_mixed_comm_adam: the ADD, psgd_aggregate_comm_dst on the residual into
 //                scratch destinations, psgd_adam_update_mp on them: the final pass updates the fp32
 //                master weights and moments and stores bf16(p') at the model parameters.
+//   wide adam    psgd_aggregate_comm_adam_wide / psgd_aggregate_mixed_comm_adam_wide (ranks 33-128): the two
+//                above with psgd_aggregate_comm's slabs in place of the scratch destinations (a wide plan
+//                has no destination-table step); the final pass is k_wide_apply_adam.
 // Every entry is a descriptor (Entry) and its arguments (Call): one preamble runs the checks in the
 // entry's documented order, one body makes the side state, asks admission (a refusal launches
 // nothing), builds the sink and hands it to the step driver of the entry's transport.
@@ -43,7 +46,10 @@ struct Entry {
     bool mp = false;  // adam over fp32 master weights of a bf16 model: `state` the residual, `peer` the
                       // masters, Call::grads16 / ws the bf16 gradients and model parameters
     bool upd() const { return sgd || adam; }
-    Adm::Kind kind() const { return mp ? Adm::F32AdamMp : adam ? Adm::F32Adam : sgd ? Adm::F32Sgd : !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense; }
+    Adm::Kind kind() const {
+        if (adam && wide) return mp ? Adm::F32AdamMpWide : Adm::F32AdamWide;
+        return mp ? Adm::F32AdamMp : adam ? Adm::F32Adam : sgd ? Adm::F32Sgd : !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense;
+    }
 };
 
 // The arguments by role. `state`: the fp32 tensors the codec runs on (a bf16 sink: the residual; else
@@ -84,7 +90,14 @@ struct Call {
 const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool sgd = false, bool adam = false) {
     *code = PSGD_ERR_VALUE;
     const int rb = p->rbucket;
-    if (adam) {
+    if (adam && wide) {  // the wide Adam entries: what the narrow ones refuse by rank
+        if (p->dtype != PSGD_F32) {
+            *code = PSGD_ERR_DTYPE;
+            return "psgd_aggregate_comm_adam_wide takes an fp32 plan";
+        }
+        if (!p->wide()) return "psgd_aggregate_comm_adam_wide serves ranks 33-128 (psgd_aggregate_comm_adam: rank buckets 1 to 32)";
+        if (p->spans.size() > 1) return "psgd_aggregate_comm_adam_wide takes a plan of one bucket";
+    } else if (adam) {
         if (p->dtype != PSGD_F32) {
             *code = PSGD_ERR_DTYPE;
             return "psgd_aggregate_comm_adam takes an fp32 plan";
@@ -125,7 +138,8 @@ const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool
 // communicator kind, asked with ntiles = 0 through the launch functions the drivers use. NoComm is
 // aggregate_ctx's context (the fused final pass where the step has one); Bf16Ingest its single-pass
 // final kernel with the ingest fold (false where the step's first pass is another one). A wide
-// plan's only sink instance is k_wide_apply_mix<rbucket> (shared terms at world size 1)
+// plan's sink instances are k_wide_apply_mix<rbucket> and k_wide_apply_adam<rbucket> (shared terms at
+// world size 1)
 bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
     OutSink sink;
     sink.sgd = kind == Adm::F32Sgd;
@@ -140,6 +154,8 @@ bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
         WideArgs a{};
         a.shared = world == 1;
         if (kind == Adm::Bf16Dense) e = launch_wide_apply_mix(p->rbucket, a, 0, nullptr, &w);
+        else if (kind == Adm::F32AdamWide || kind == Adm::F32AdamMpWide)
+            e = launch_wide_apply_adam(p->rbucket, kind == Adm::F32AdamMpWide, a, WideAdamDst{}, 0, nullptr, &w);
     } else if (comm == Adm::NoComm) {
         StepCtx c = world1_ctx(out_ctx(&sink));
         c.mix_in = kind == Adm::Bf16Ingest && p->mix_ingest_on;
@@ -178,6 +194,9 @@ bool admitted(psgd_plan* p, Adm::Kind kind, Adm::Comm comm) {
 // per communicator kind; the wide entries and the fp32 tables are eligible as a whole plan or not
 bool eligible(psgd_plan* p, const Entry& e, int world) {
     if (e.via == Entry::World1 && !e.wide) return admitted(p, e.kind(), Adm::NoComm);
+    // a wide plan has no destination-table instances: its Adam entries are defined against
+    // psgd_aggregate_comm's slab, and ask for k_wide_apply_adam of the communicator kind alone
+    if (e.wide && e.adam) return admitted(p, e.kind(), world == 1 ? Adm::One : Adm::Many);
     // an update entry is defined as the destination-table step followed by psgd_sgd_update /
     // psgd_adam_update: it serves the plans whose destination instances are admitted too
     if (e.upd() && !(admitted(p, Adm::F32Tables, Adm::Many) && admitted(p, Adm::F32Tables, Adm::One))) return false;
@@ -311,7 +330,7 @@ int body(const Entry& e, const Call& c, bool* refused) {
     if (e.upd()) {  // its tables are psgd_plan::Sgd's / Adam's (psgd_sgd.cpp, psgd_adam.cpp), and there is
                     // no transport but the communicator
         if (int st = refresh_pointers(p, c.state, s)) return st;
-        if (!eligible(p, e, 1)) {
+        if (!eligible(p, e, c.comm ? comm_world(c.comm) : 1)) {  // the narrow entries ask both kinds
             *refused = true;
             return fail(PSGD_ERR_VALUE, std::string(e.name) + ": no admitted update instance of this plan's final pass "
                                                               "(two waves per SIMD, no scratch)");
@@ -417,6 +436,8 @@ const Entry kIpcDst{"psgd_aggregate_ipc_dst", Entry::Xchg, false, true, false};
 const Entry kCommSgd{"psgd_aggregate_comm_sgd", Entry::Comm, false, true, false, true};
 const Entry kCommAdam{"psgd_aggregate_comm_adam", Entry::Comm, false, true, false, false, true};
 const Entry kMixedCommAdam{"psgd_aggregate_mixed_comm_adam", Entry::Comm, false, true, false, false, true, true};
+const Entry kCommAdamWide{"psgd_aggregate_comm_adam_wide", Entry::Comm, true, true, false, false, true};
+const Entry kMixedCommAdamWide{"psgd_aggregate_mixed_comm_adam_wide", Entry::Comm, true, true, false, false, true, true};
 
 }  // namespace
 
@@ -560,6 +581,54 @@ int psgd_aggregate_mixed_comm_adam(psgd_plan* p, void* const* grads_bf16, void* 
     c.ws = params_bf16;
     c.unc_ws = unc_params_bf16;
     return run(kMixedCommAdam, c);
+}
+
+int psgd_plan_adam_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, false, true, &code, false, true)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kCommAdamWide, world) ? 1 : 0; });
+}
+
+int psgd_aggregate_comm_adam_wide(psgd_plan* p, void* const* grads, void* const* params, void* const* ms,
+                                  void* const* vs, const psgd_adam_hyper* hyper, int64_t step, psgd_flat* f,
+                                  void* const* unc, void* const* unc_params, void* const* unc_ms, void* const* unc_vs,
+                                  psgd_comm* comm, void* stream) {
+    Call c{p, grads, params, nullptr, step, f, unc, unc_params, nullptr, comm, stream};
+    c.bufs = ms;
+    c.unc_bufs = unc_ms;
+    c.vs = vs;
+    c.unc_vs = unc_vs;
+    c.adam = hyper;
+    return run(kCommAdamWide, c);
+}
+
+int psgd_plan_mixed_adam_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, false, true, &code, false, true)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kMixedCommAdamWide, world) ? 1 : 0; });
+}
+
+int psgd_aggregate_mixed_comm_adam_wide(psgd_plan* p, void* const* grads_bf16, void* const* residual,
+                                        void* const* params_bf16, void* const* masters, void* const* ms,
+                                        void* const* vs, const psgd_adam_hyper* hyper, int64_t step, psgd_flat* f,
+                                        void* const* unc_bf16, void* const* unc_residual, void* const* unc_params_bf16,
+                                        void* const* unc_masters, void* const* unc_ms, void* const* unc_vs,
+                                        psgd_comm* comm, void* stream) {
+    Call c{p, residual, masters, nullptr, step, f, unc_residual, unc_masters, nullptr, comm, stream};
+    c.bufs = ms;
+    c.unc_bufs = unc_ms;
+    c.vs = vs;
+    c.unc_vs = unc_vs;
+    c.adam = hyper;
+    c.grads16 = grads_bf16;
+    c.unc_grads16 = unc_bf16;
+    c.ws = params_bf16;
+    c.unc_ws = unc_params_bf16;
+    return run(kMixedCommAdamWide, c);
 }
 
 int psgd_aggregate_mixed_flat(psgd_plan* p, void* const* grads_bf16, void* const* residual, void* out_bf16, int64_t step,

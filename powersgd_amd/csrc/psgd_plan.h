@@ -421,7 +421,9 @@ struct psgd_plan {
             Bf16Dense, Bf16Tables, F32Tables, Bf16Ingest /* world size 1, the single-pass final kernel */,
             F32Sgd /* the update instances of psgd_aggregate_comm_sgd */,
             F32Adam /* the Adam instances of psgd_aggregate_comm_adam */,
-            F32AdamMp /* the master-weight instances of psgd_aggregate_mixed_comm_adam */, kKinds
+            F32AdamMp /* the master-weight instances of psgd_aggregate_mixed_comm_adam */,
+            F32AdamWide /* k_wide_apply_adam of psgd_aggregate_comm_adam_wide */,
+            F32AdamMpWide /* its master-weight form, psgd_aggregate_mixed_comm_adam_wide */, kKinds
         };
         enum Comm { NoComm /* aggregate_ctx */, Many /* world size > 1 */, One /* a 1-rank communicator */, kComms };
         uint64_t key = ~uint64_t(0);

@@ -219,9 +219,13 @@ int compress_wide(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hi
     return PSGD_OK;
 }
 
-// `mix` (a bf16 sink: psgd_aggregate_mixed_wide[_comm]): `grads` the fp32 residual, `out` bf16: the
-// same arguments to k_wide_apply_mix
-int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s, bool mix) {
+// A bf16 sink (psgd_aggregate_mixed_wide[_comm]): `grads` the fp32 residual, `out` bf16: the same
+// arguments to k_wide_apply_mix. An Adam sink (psgd_aggregate_comm_adam_wide, _mixed_comm_adam_wide):
+// no output; k_wide_apply_adam updates the sink's tensors, and the context's flat items (the flat
+// tail's update items) lead its launch
+int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s,
+                    const StepCtx& c) {
+    const OutSink* sink = c.sink;
     if (int st = refresh_pointers(p, grads, s)) return st;
     const int I = p->iters;
     WideArgs a{};
@@ -239,8 +243,14 @@ int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, i
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     if (int st = timing_begin(p, s, &ev, true)) return st;
     TimedScope ts(ev);
-    if (mix) PSGD_HIP(launch_wide_apply_mix(p->rbucket, a, int(p->wide_apply.size()), s, nullptr));
-    else PSGD_HIP(launch_wide_apply(p->dtype, p->rbucket, a, int(p->wide_apply.size()), s));
+    if (sink && sink->adam) {
+        WideAdamDst x{sink->dst, sink->adam_mp_dst(), c.fl ? *c.fl : FlatArgs{}};
+        PSGD_HIP(launch_wide_apply_adam(p->rbucket, sink->adam_mp, a, x, int(p->wide_apply.size()), s, nullptr));
+    } else if (sink && sink->bf16) {
+        PSGD_HIP(launch_wide_apply_mix(p->rbucket, a, int(p->wide_apply.size()), s, nullptr));
+    } else {
+        PSGD_HIP(launch_wide_apply(p->dtype, p->rbucket, a, int(p->wide_apply.size()), s));
+    }
     return PSGD_OK;
 }
 
@@ -587,7 +597,7 @@ int psgd::aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStrea
 int psgd::decompress_impl(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s,
                           StepCtx c) {
     if (p->f64()) return decompress_f64(p, grads, out, step, world, s);
-    if (p->wide()) return decompress_wide(p, grads, out, step, world, s, c.sink && c.sink->bf16);
+    if (p->wide()) return decompress_wide(p, grads, out, step, world, s, c);
     const OutRoute o = p->out_route(step, world, c);
     if (o.kind == OutRoute::None) return PSGD_OK;  // output written by the fused last iteration
     if (int st = refresh_pointers(p, grads, s)) return st;

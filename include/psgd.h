@@ -874,6 +874,50 @@ int psgd_aggregate_mixed_comm_adam_wide(psgd_plan* plan, void* const* grads_bf16
                                         void* const* unc_vs, psgd_comm* comm, void* stream);
 int psgd_plan_mixed_adam_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
 
+/* ------- the DDP hook's one-call completions at ranks 33-128 (a wide plan, psgd_plan_is_wide) ------- */
+/* psgd_aggregate_comm_dst_wide: psgd_aggregate_comm_dst's arguments on a wide plan, which that entry
+ * refuses. DEFINED as, and bit for bit equal to (every destination, the residual, the P/Q state; the
+ * same kernels before the final pass, the same collectives in the same order):
+ *   1. psgd_aggregate_comm(plan, grads, out, step, flat, unc, flat_out, comm) into scratch slabs
+ *   2. dst[i][e] = out_i[e] for every tensor i of the plan, unc_dst[k][e] = flat_k[e] for every
+ *      tensor k of the flat plan
+ * No slab is written and no gather runs. Where it runs: the final pass as k_wide_apply_dst
+ * (psgd_wide_dst.hip): k_wide_apply<float>'s tile and MFMA sequence with the factor blocks staged in
+ * LDS (psgd_aggregate_mixed_wide's pass), so the residual and the average of an element have
+ * k_wide_apply's bits; the average is stored at the same element of the tensor's own destination.
+ * A destination is dense and 4-byte aligned or better: a tile stores 16 bytes per row quad where
+ * m % 4 == 0 and the destination is 16-byte aligned, else four 4-byte stores, chosen once per tile
+ * from the destination alone; every store is predicated on its own row and column, nothing outside
+ * a destination's numel elements is written. Plain stores, as k_wide_apply's. The flat tail is packed
+ * in a launch of its own into the plan's fp32 stage, summed there by the last collective, and copied
+ * to unc_dst by the leading workgroups of the final launch. `comm` NULL: world size 1, no
+ * collectives. The destination tables are kept on the device and re-uploaded only when they change.
+ * Eligible: an fp32 wide plan of one bucket whose instance for the communicator kind asked (one rank:
+ * shared terms; else two term sets) is admitted (two waves per SIMD, no scratch; asked once per
+ * plan). psgd_plan_dst_wide_ok: *ok = 1 for such a plan at `world`. A refusal launches nothing and
+ * issues no collective.
+ * Refusals: psgd_aggregate_comm_dst's codes in its order (but `comm` may be NULL); a plan that is
+ * not wide: PSGD_ERR_VALUE. psgd_clip_dst does not serve a wide plan (psgd_plan_clip_dst_ok is 0). */
+int psgd_aggregate_comm_dst_wide(psgd_plan* plan, void* const* grads, void* const* dst, int64_t step,
+                                 psgd_flat* flat, void* const* unc, void* const* unc_dst, psgd_comm* comm,
+                                 void* stream);
+int psgd_plan_dst_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
+
+/* psgd_aggregate_mixed_comm_dst_wide: psgd_aggregate_mixed_comm_dst's arguments on a wide plan.
+ * `residual` already holds residual + gradients (the hook adds each bucket on arrival): no ADD runs.
+ * DEFINED as, and bit for bit equal to: psgd_aggregate_comm on the residual into scratch fp32
+ * slabs, then dst_bf16[i][e] = bf16(out_i[e]) and unc_dst_bf16[k][e] = bf16(flat_k[e]), rounded to
+ * nearest even. The final pass is the bf16 form of k_wide_apply_dst: the fp32 average is pinned as a
+ * value of its own, then rounded; one packed 8-byte store per row quad where m % 4 == 0 and the
+ * destination is 8-byte aligned, else four 2-byte stores. A destination is dense and 2-byte aligned
+ * or better. The flat tail's round items lead the final launch. Eligibility and the query
+ * (psgd_plan_mixed_dst_wide_ok) as above; refusals: psgd_aggregate_mixed_comm_dst's codes in its
+ * order (`comm` may be NULL); a plan that is not wide: PSGD_ERR_VALUE. */
+int psgd_aggregate_mixed_comm_dst_wide(psgd_plan* plan, void* const* residual, void* const* dst_bf16, int64_t step,
+                                       psgd_flat* flat, void* const* unc_residual, void* const* unc_dst_bf16,
+                                       psgd_comm* comm, void* stream);
+int psgd_plan_mixed_dst_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
+
 /* ------------------------ global-norm clipping of a step's averages (clip_grad_norm_) ---------- */
 /* torch.nn.utils.clip_grad_norm_ (L2) over everything a step returned, on the stream, with no host
  * synchronisation: norm = sqrt(sum of squares of the compressed averages `out` and of the dense

@@ -113,6 +113,10 @@ _SIGNATURES = {
     "psgd_plan_adam_wide_ok": ([_vp, _i64, _i32, _P_i32], _i32),
     "psgd_aggregate_mixed_comm_adam_wide": ([_vp] * 8 + [_i64] + [_vp] * 9, _i32),
     "psgd_plan_mixed_adam_wide_ok": ([_vp, _i64, _i32, _P_i32], _i32),
+    "psgd_aggregate_comm_dst_wide": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_dst_wide_ok": ([_vp, _i64, _i32, _P_i32], _i32),
+    "psgd_aggregate_mixed_comm_dst_wide": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_mixed_dst_wide_ok": ([_vp, _i64, _i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -379,6 +383,22 @@ class Plan:
                                                   flat._h if flat is not None else None, unc_residual, unc_dst_bf16,
                                                   comm._h if comm is not None else None, stream))
 
+    def mixed_dst_wide_ok(self, step: int, world: int) -> int:
+        """1 where ``aggregate_mixed_comm_dst_wide`` serves this plan at ``world`` (psgd_plan_mixed_dst_wide_ok:
+        an fp32 wide plan of one bucket whose k_wide_apply_dst instance is admitted)."""
+        ok = _i32()
+        check(lib().psgd_plan_mixed_dst_wide_ok(self._h, step, world, ctypes.byref(ok)))
+        return int(ok.value)
+
+    def aggregate_mixed_comm_dst_wide(self, residual, dst_bf16, step: int, comm: Optional["Comm"], stream: int,
+                                      flat=None, unc_residual=None, unc_dst_bf16=None) -> None:
+        """psgd_aggregate_mixed_comm_dst_wide: ``aggregate_mixed_comm_dst`` on a plan of ranks 33-128
+        (``aggregate_comm`` on the residual, then the bf16 rounding of every average at its destination).
+        ``comm`` None: world size 1 without collectives."""
+        check(lib().psgd_aggregate_mixed_comm_dst_wide(self._h, residual, dst_bf16, step,
+                                                       flat._h if flat is not None else None, unc_residual,
+                                                       unc_dst_bf16, comm._h if comm is not None else None, stream))
+
     # --- the fp32 averages stored at per-tensor destinations (the default DDP hook's one-call completion)
     def dst_ok(self, step: int, world: int) -> int:
         """1 where ``aggregate_comm_dst`` / ``aggregate_ipc_dst`` serve this plan (psgd_plan_dst_ok: a
@@ -394,6 +414,21 @@ class Plan:
         anything is launched or any collective issued."""
         check(lib().psgd_aggregate_comm_dst(self._h, grads, dst, step, flat._h if flat is not None else None, unc,
                                             unc_dst, comm._h if comm is not None else None, stream))
+
+    def dst_wide_ok(self, step: int, world: int) -> int:
+        """1 where ``aggregate_comm_dst_wide`` serves this plan at ``world`` (psgd_plan_dst_wide_ok: an fp32
+        wide plan of one bucket whose k_wide_apply_dst instance is admitted)."""
+        ok = _i32()
+        check(lib().psgd_plan_dst_wide_ok(self._h, step, world, ctypes.byref(ok)))
+        return int(ok.value)
+
+    def aggregate_comm_dst_wide(self, grads, dst, step: int, comm: Optional["Comm"], stream: int, flat=None,
+                                unc=None, unc_dst=None) -> None:
+        """psgd_aggregate_comm_dst_wide: ``aggregate_comm_dst`` on a plan of ranks 33-128 (``aggregate_comm``
+        followed by a copy of every average to its destination, with no slab written). ``comm`` None:
+        world size 1 without collectives."""
+        check(lib().psgd_aggregate_comm_dst_wide(self._h, grads, dst, step, flat._h if flat is not None else None,
+                                                 unc, unc_dst, comm._h if comm is not None else None, stream))
 
     # --- the fused SGD step: the final pass applies the update to the weights
     def sgd_ok(self, step: int, world: int, momentum_used: bool = True) -> int:

@@ -9,6 +9,7 @@
 // copies of the tile body, chosen once per tile, workgroup-uniform. Every store goes through a
 // descriptor that spans the tile's rows of its own tensor: nothing can land on a bucket neighbour.
 #include "psgd_final.cuh"
+#include "psgd_flat_copy.cuh"  // flat_copy_item: the flat tail's copy items
 
 namespace psgd {
 
@@ -18,33 +19,6 @@ __device__ __forceinline__ bool dst_al16(const ApplyArgs& a, const MatDesc& d, c
     const uintptr_t o = reinterpret_cast<uintptr_t>(a.odst[d.tensor]) +
                         uintptr_t(int64_t(t.chunk) * d.chunk_rows * d.m) * sizeof(float);
     return (o & 15) == 0;
-}
-
-// Copy item: the item's elements of the all-reduced flat tail (`stage`, the flat plan's layout)
-// to the tensor's own destination dst[en.tensor] (the flat plan's order; 4-byte aligned: element
-// stores), bits unchanged. flat_round_item's shape without the rounding: the descriptor spans the
-// item's elements of that tensor alone.
-template <int NT>
-__device__ __forceinline__ void flat_copy_item(const FlatArgs& a, const float* stage, int item, void* const* dst) {
-    constexpr int PER = kFlatItem / NT;
-    const FlatItem it = a.items[item];
-    const FlatEntry en = a.entries[it.entry];
-    const gptr<const float> x = gconst<float>(stage) + en.off;
-    const uint32_t cnt = uint32_t(en.numel - it.start < kFlatItem ? en.numel - it.start : kFlatItem);
-    const rsrc_t rf = make_rsrc(static_cast<float*>(dst[en.tensor]) + it.start, cnt * 4u);
-    float v[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int64_t j = it.start + int64_t(q) * NT + threadIdx.x;
-        v[q] = x[j < en.numel ? j : 0];  // clamped, unconditional
-    }
-#pragma unroll
-    for (int q = 0; q < PER; ++q) keep(v[q]);
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int64_t j = it.start + int64_t(q) * NT + threadIdx.x;
-        if (j < en.numel) StIo<float>::st1(rf, uint32_t(int64_t(q) * NT + threadIdx.x) * 4u, v[q]);
-    }
 }
 
 // k_apply<float, R, NI, SHARED, ONT> into a.odst; the copy items of the flat tail are its leading

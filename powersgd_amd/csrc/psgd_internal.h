@@ -653,6 +653,25 @@ struct WideAdamDst {
 hipError_t launch_wide_apply_adam(int R, bool mp, const WideArgs& a, const WideAdamDst& x, int ntiles, hipStream_t s,
                                   int* waves);
 
+// psgd_aggregate_comm_dst_wide / psgd_aggregate_mixed_comm_dst_wide (ranks 33-128, the DDP hook's
+// completions): the same pass whose epilogue stores each tensor's average at the tensor's own
+// destination (a view into a DDP bucket: dense; fp32 4-byte aligned or better, bf16 2-byte) at the
+// element where k_wide_apply<float> would have stored it in the slab. `dst` in the plan's tensor
+// order, `unc_dst` in the flat plan's; `stage` the plan-owned fp32 buffer the last collective summed
+// the flat tail in; `flat` the flat tail's copy items (fp32) or round items (bf16), which lead the
+// launch.
+struct WideDst {
+    void* const* dst;
+    void* const* unc_dst;
+    const float* stage;
+    FlatArgs flat;
+};
+// psgd_wide_dst.hip. `bf16`: the destinations take the bf16 rounding. ntiles + items == 0: no launch;
+// `*waves` (if non-null) receives the resident waves per SIMD of the instance that would run, 0 with
+// scratch.
+hipError_t launch_wide_apply_dst(int R, bool bf16, const WideArgs& a, const WideDst& x, int ntiles, hipStream_t s,
+                                 int* waves);
+
 // One-shot all-reduce over IPC-mapped exchange buffers (psgd_aggregate_ipc). Every rank's
 // exchange buffer: kXchgHeader bytes of per-iteration epoch flags (uint64, one per iteration),
 // then two parities x iterations slots of xchg_slot floats each; the producer kernels (k_reduce,

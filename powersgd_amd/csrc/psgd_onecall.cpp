@@ -25,6 +25,10 @@
 //   wide adam    psgd_aggregate_comm_adam_wide / psgd_aggregate_mixed_comm_adam_wide (ranks 33-128): the two
 //                above with psgd_aggregate_comm's slabs in place of the scratch destinations (a wide plan
 //                has no destination-table step); the final pass is k_wide_apply_adam.
+//   wide tables  psgd_aggregate_comm_dst_wide / psgd_aggregate_mixed_comm_dst_wide (ranks 33-128), the DDP
+//                hook's completions on a wide plan: psgd_aggregate_comm into scratch slabs, then every
+//                average copied (bf16: rounded) to the tensor's own destination; the final pass is
+//                k_wide_apply_dst, which stores there and writes no slab.
 // Every entry is a descriptor (Entry) and its arguments (Call): one preamble runs the checks in the
 // entry's documented order, one body makes the side state, asks admission (a refusal launches
 // nothing), builds the sink and hands it to the step driver of the entry's transport.
@@ -46,7 +50,9 @@ struct Entry {
     bool mp = false;  // adam over fp32 master weights of a bf16 model: `state` the residual, `peer` the
                       // masters, Call::grads16 / ws the bf16 gradients and model parameters
     bool upd() const { return sgd || adam; }
+    bool wide_dst() const { return wide && tables && !upd(); }  // the wide destination-table entries
     Adm::Kind kind() const {
+        if (wide_dst()) return bf16 ? Adm::Bf16TablesWide : Adm::F32TablesWide;
         if (adam && wide) return mp ? Adm::F32AdamMpWide : Adm::F32AdamWide;
         return mp ? Adm::F32AdamMp : adam ? Adm::F32Adam : sgd ? Adm::F32Sgd : !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense;
     }
@@ -87,10 +93,25 @@ struct Call {
 // tiles) and 16 / 32 (matrix-core tiles, psgd_mixed_mfma.hip), not 8 (the VALU tile whose
 // register-cached two-set instances sit at the scratch edge); the wide entries: what those refuse by
 // rank. fp32 tables: fp32, one bucket, not wide
-const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool sgd = false, bool adam = false) {
+const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool sgd = false, bool adam = false,
+                       bool wide_dst = false) {
     *code = PSGD_ERR_VALUE;
     const int rb = p->rbucket;
-    if (adam && wide) {  // the wide Adam entries: what the narrow ones refuse by rank
+    if (wide_dst && !bf16) {  // the wide destination-table entries: what the narrow ones refuse by rank
+        if (p->dtype != PSGD_F32) {
+            *code = PSGD_ERR_DTYPE;
+            return "psgd_aggregate_comm_dst_wide takes an fp32 plan";
+        }
+        if (!p->wide()) return "psgd_aggregate_comm_dst_wide serves ranks 33-128 (psgd_aggregate_comm_dst: rank buckets 1 to 32)";
+        if (p->spans.size() > 1) return "psgd_aggregate_comm_dst_wide takes a plan of one bucket";
+    } else if (wide_dst) {
+        if (p->dtype != PSGD_F32)
+            return "psgd_aggregate_mixed_comm_dst_wide takes an fp32 plan (the fp32 residual of bf16 gradients)";
+        if (!p->wide())
+            return "psgd_aggregate_mixed_comm_dst_wide serves ranks 33-128 (psgd_aggregate_mixed_comm_dst: rank buckets 1, "
+                   "2, 4, 16 and 32)";
+        if (p->spans.size() > 1) return "psgd_aggregate_mixed_comm_dst_wide takes a plan of one bucket";
+    } else if (adam && wide) {  // the wide Adam entries: what the narrow ones refuse by rank
         if (p->dtype != PSGD_F32) {
             *code = PSGD_ERR_DTYPE;
             return "psgd_aggregate_comm_adam_wide takes an fp32 plan";
@@ -138,8 +159,8 @@ const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool
 // communicator kind, asked with ntiles = 0 through the launch functions the drivers use. NoComm is
 // aggregate_ctx's context (the fused final pass where the step has one); Bf16Ingest its single-pass
 // final kernel with the ingest fold (false where the step's first pass is another one). A wide
-// plan's sink instances are k_wide_apply_mix<rbucket> and k_wide_apply_adam<rbucket> (shared terms at
-// world size 1)
+// plan's sink instances are k_wide_apply_mix<rbucket>, k_wide_apply_adam<rbucket> and
+// k_wide_apply_dst<rbucket> (shared terms at world size 1)
 bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
     OutSink sink;
     sink.sgd = kind == Adm::F32Sgd;
@@ -156,6 +177,8 @@ bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
         if (kind == Adm::Bf16Dense) e = launch_wide_apply_mix(p->rbucket, a, 0, nullptr, &w);
         else if (kind == Adm::F32AdamWide || kind == Adm::F32AdamMpWide)
             e = launch_wide_apply_adam(p->rbucket, kind == Adm::F32AdamMpWide, a, WideAdamDst{}, 0, nullptr, &w);
+        else if (kind == Adm::F32TablesWide || kind == Adm::Bf16TablesWide)
+            e = launch_wide_apply_dst(p->rbucket, kind == Adm::Bf16TablesWide, a, WideDst{}, 0, nullptr, &w);
     } else if (comm == Adm::NoComm) {
         StepCtx c = world1_ctx(out_ctx(&sink));
         c.mix_in = kind == Adm::Bf16Ingest && p->mix_ingest_on;
@@ -195,8 +218,9 @@ bool admitted(psgd_plan* p, Adm::Kind kind, Adm::Comm comm) {
 bool eligible(psgd_plan* p, const Entry& e, int world) {
     if (e.via == Entry::World1 && !e.wide) return admitted(p, e.kind(), Adm::NoComm);
     // a wide plan has no destination-table instances: its Adam entries are defined against
-    // psgd_aggregate_comm's slab, and ask for k_wide_apply_adam of the communicator kind alone
-    if (e.wide && e.adam) return admitted(p, e.kind(), world == 1 ? Adm::One : Adm::Many);
+    // psgd_aggregate_comm's slab, and ask for k_wide_apply_adam of the communicator kind alone; its
+    // destination-table entries likewise for k_wide_apply_dst
+    if (e.wide && (e.adam || e.tables)) return admitted(p, e.kind(), world == 1 ? Adm::One : Adm::Many);
     // an update entry is defined as the destination-table step followed by psgd_sgd_update /
     // psgd_adam_update: it serves the plans whose destination instances are admitted too
     if (e.upd() && !(admitted(p, Adm::F32Tables, Adm::Many) && admitted(p, Adm::F32Tables, Adm::One))) return false;
@@ -263,7 +287,8 @@ void release(psgd_plan::Side*& slot) {
 // Leaves c.f null where there is no flat tail
 int preamble(const Entry& e, Call& c) {
     const psgd_plan* p = c.p;
-    const bool args = p && c.state && c.peer && (e.tables || c.out) && (e.via != Entry::Comm || c.comm || e.upd()) &&
+    const bool args = p && c.state && c.peer && (e.tables || c.out) &&
+                      (e.via != Entry::Comm || c.comm || e.upd() || e.wide_dst()) &&
                       (!e.sgd || c.hyper) && (!e.adam || (c.bufs && c.vs && c.adam)) && (!e.mp || (c.grads16 && c.ws));
     if (e.via == Entry::Xchg) {
         if (!args) return fail(PSGD_ERR_VALUE, "null argument");
@@ -275,7 +300,7 @@ int preamble(const Entry& e, Call& c) {
     if (!e.tables)
         if (int st = check_out(c.out)) return st;
     int code = PSGD_ERR_VALUE;
-    const char* why = ineligible(p, e.bf16, e.wide, &code, e.sgd, e.adam);
+    const char* why = ineligible(p, e.bf16, e.wide, &code, e.sgd, e.adam, e.wide_dst());
     if (why && !e.bf16) return fail(code, why);
     if (!c.f || c.f->total == 0) c.f = nullptr;
     if (const psgd_flat* f = c.f) {
@@ -358,10 +383,11 @@ int body(const Entry& e, const Call& c, bool* refused) {
     // The wide kernels test each tensor's alignment themselves
     if (!e.wide)
         if (int st = refresh_pointers(p, c.state, s)) return st;
-    const int world = e.via == Entry::Comm ? comm_world(c.comm) : e.via == Entry::Xchg ? p->ipc_world : 1;
+    const int world = e.via == Entry::Comm ? (c.comm ? comm_world(c.comm) : 1) : e.via == Entry::Xchg ? p->ipc_world : 1;
     if (!eligible(p, e, world)) {
         *refused = true;
-        const char* what = e.wide     ? "k_wide_apply_mix for this plan's rank bucket"
+        const char* what = e.wide_dst() ? "k_wide_apply_dst for this plan's rank bucket"
+                           : e.wide   ? "k_wide_apply_mix for this plan's rank bucket"
                            : e.tables ? "destination-table instance of this plan's final pass"
                                       : "bf16-output instance of this plan's final pass";
         return fail(PSGD_ERR_VALUE, std::string(e.name) + ": no admitted " + what + " (two waves per SIMD, no scratch)");
@@ -438,6 +464,8 @@ const Entry kCommAdam{"psgd_aggregate_comm_adam", Entry::Comm, false, true, fals
 const Entry kMixedCommAdam{"psgd_aggregate_mixed_comm_adam", Entry::Comm, false, true, false, false, true, true};
 const Entry kCommAdamWide{"psgd_aggregate_comm_adam_wide", Entry::Comm, true, true, false, false, true};
 const Entry kMixedCommAdamWide{"psgd_aggregate_mixed_comm_adam_wide", Entry::Comm, true, true, false, false, true, true};
+const Entry kCommDstWide{"psgd_aggregate_comm_dst_wide", Entry::Comm, true, true, false};
+const Entry kMixedCommDstWide{"psgd_aggregate_mixed_comm_dst_wide", Entry::Comm, true, true, true};
 
 }  // namespace
 
@@ -693,6 +721,34 @@ int psgd_aggregate_comm_dst(psgd_plan* p, void* const* grads, void* const* dst, 
 int psgd_aggregate_ipc_dst(psgd_plan* p, void* const* grads, void* const* dst, int64_t step, psgd_flat* f,
                            void* const* unc, void* const* unc_dst, void* stream) {
     return run(kIpcDst, Call{p, grads, dst, nullptr, step, f, unc, unc_dst, nullptr, nullptr, stream});
+}
+
+int psgd_plan_dst_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, false, true, &code, false, false, true)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kCommDstWide, world) ? 1 : 0; });
+}
+
+int psgd_aggregate_comm_dst_wide(psgd_plan* p, void* const* grads, void* const* dst, int64_t step, psgd_flat* f,
+                                 void* const* unc, void* const* unc_dst, psgd_comm* comm, void* stream) {
+    return run(kCommDstWide, Call{p, grads, dst, nullptr, step, f, unc, unc_dst, nullptr, comm, stream});
+}
+
+int psgd_plan_mixed_dst_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, true, true, &code, false, false, true)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kMixedCommDstWide, world) ? 1 : 0; });
+}
+
+int psgd_aggregate_mixed_comm_dst_wide(psgd_plan* p, void* const* residual, void* const* dst_bf16, int64_t step,
+                                       psgd_flat* f, void* const* unc_residual, void* const* unc_dst_bf16,
+                                       psgd_comm* comm, void* stream) {
+    return run(kMixedCommDstWide, Call{p, residual, dst_bf16, nullptr, step, f, unc_residual, unc_dst_bf16, nullptr,
+                                       comm, stream});
 }
 
 }  // extern "C"

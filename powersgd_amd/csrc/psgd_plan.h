@@ -423,7 +423,9 @@ struct psgd_plan {
             F32Adam /* the Adam instances of psgd_aggregate_comm_adam */,
             F32AdamMp /* the master-weight instances of psgd_aggregate_mixed_comm_adam */,
             F32AdamWide /* k_wide_apply_adam of psgd_aggregate_comm_adam_wide */,
-            F32AdamMpWide /* its master-weight form, psgd_aggregate_mixed_comm_adam_wide */, kKinds
+            F32AdamMpWide /* its master-weight form, psgd_aggregate_mixed_comm_adam_wide */,
+            F32TablesWide /* k_wide_apply_dst of psgd_aggregate_comm_dst_wide */,
+            Bf16TablesWide /* its bf16 form, psgd_aggregate_mixed_comm_dst_wide */, kKinds
         };
         enum Comm { NoComm /* aggregate_ctx */, Many /* world size > 1 */, One /* a 1-rank communicator */, kComms };
         uint64_t key = ~uint64_t(0);
@@ -865,7 +867,8 @@ inline OutRoute psgd_plan::out_route(int64_t step, int world, const StepCtx& c) 
     o.timed = o.kind == OutRoute::Apply;
     o.tables = c.sink && c.sink->tables;
     o.flat = o.kind == OutRoute::Apply || bf16 || o.tables;
-    o.rounds = bf16 && !wide() && (o.kind == OutRoute::Lowrank || o.inst == OutRoute::MixW);
+    // (a wide plan: k_wide_apply_dst carries them, k_wide_apply_mix takes none)
+    o.rounds = bf16 && (wide() ? o.tables : o.kind == OutRoute::Lowrank || o.inst == OutRoute::MixW);
     // fused (world size 1): the reduced factor was never copied to history slot 2
     o.reduced_slot = fused_norm(c.fuse, 1) ? 1 : 2;
     return o;

@@ -92,14 +92,16 @@ class PowerSGDState(metaclass=_ClipKeyword):
     DDP bucket, so no fp32 output slab is written and no per-bucket gather runs. Bit for bit the
     three stages it replaces. It applies on a compressing step, in a process group that runs over
     the library's own communicator or over the IPC exchange (not ``PSGD_COMM=torch``, not gloo
-    without the IPC exchange), on a plan the call serves (rank bucket 1 / 2 / 4 / 16 / 32; not 8, not ranks above 32); every other
+    without the IPC exchange), on a plan the call serves (rank bucket 1 / 2 / 4 / 16 / 32, not 8;
+    ranks 33-128 through psgd_aggregate_mixed_comm_dst_wide, over the library's communicator only); every other
     completion runs the three stages (``fused_folds()`` tells which).
 
     ``state.direct_store = True`` (float32 parameters with a float32 residual, ``fused=False``; set
     before the first backward) is the same one-call completion for the default fp32 hook
     (psgd_aggregate_comm_dst, or psgd_aggregate_ipc_dst under ``PSGD_COMM=ipc``): the final pass
     stores each parameter's fp32 average straight into its view of its DDP bucket, at rank buckets
-    1 to 32. Bit for bit the three stages; ``direct_store_applies()`` tells whether the next
+    1 to 32, and at ranks 33-128 (psgd_aggregate_comm_dst_wide) over the library's communicator, where
+    ``max_grad_norm`` keeps the three stages. Bit for bit the three stages; ``direct_store_applies()`` tells whether the next
     completion takes it (a compressing step, the library's communicator or the IPC exchange, a plan
     ``Plan.dst_ok`` reports 1 for). Opt-in: the default is ``False``.
 
@@ -367,6 +369,8 @@ class PowerSGDState(metaclass=_ClipKeyword):
                 return False
             world = comm.world
         plan = inner._powersgd._plan
+        if plan.is_wide():  # ranks 33-128: psgd_aggregate_mixed_comm_dst_wide, over the communicator only
+            return not self._fused_ipc() and plan.mixed_dst_wide_ok(0, world) == 1 and plan.mixed_dst_wide_ok(1, world) == 1
         return plan.mixed_folds_dst(0, world) == 1 and plan.mixed_folds_dst(1, world) == 1
 
     def fused_folds(self):
@@ -398,9 +402,9 @@ class PowerSGDState(metaclass=_ClipKeyword):
             codec._plan.aggregate_mixed_ipc_dst(inner._table.comp_addr(), self._dst_table.comp_addr(),
                                                 codec.step_counter, _stream(self.residual.device), **kw)
         else:
-            codec._plan.aggregate_mixed_comm_dst(inner._table.comp_addr(), self._dst_table.comp_addr(),
-                                                 codec.step_counter, self._fused_comm(), _stream(self.residual.device),
-                                                 **kw)
+            run = codec._plan.aggregate_mixed_comm_dst_wide if codec._plan.is_wide() else codec._plan.aggregate_mixed_comm_dst
+            run(inner._table.comp_addr(), self._dst_table.comp_addr(), codec.step_counter, self._fused_comm(),
+                _stream(self.residual.device), **kw)
         codec.step_counter += 1
         pending, self._pending = self._pending, []
         self._seen = [False] * len(self.params)
@@ -431,6 +435,8 @@ class PowerSGDState(metaclass=_ClipKeyword):
         plan = inner._powersgd._plan
         if inner.max_grad_norm is not None and plan.clip_dst_ok() != 1:
             return False
+        if plan.is_wide():  # ranks 33-128: psgd_aggregate_comm_dst_wide, over the communicator only
+            return not self._fused_ipc() and plan.dst_wide_ok(0, world) == 1 and plan.dst_wide_ok(1, world) == 1
         return plan.dst_ok(0, world) == 1 and plan.dst_ok(1, world) == 1
 
     def _complete_direct(self) -> None:
@@ -457,8 +463,8 @@ class PowerSGDState(metaclass=_ClipKeyword):
             world = dist.get_world_size()
         else:
             comm = self._fused_comm()
-            codec._plan.aggregate_comm_dst(inner._table.comp_addr(), self._dst_table.comp_addr(), codec.step_counter,
-                                           comm, stream, **kw)
+            run = codec._plan.aggregate_comm_dst_wide if codec._plan.is_wide() else codec._plan.aggregate_comm_dst
+            run(inner._table.comp_addr(), self._dst_table.comp_addr(), codec.step_counter, comm, stream, **kw)
             world = comm.world
         if inner.max_grad_norm is not None:
             ckw = dict(flat=kw["flat"], unc_dst=kw["unc_dst"]) if kw else {}

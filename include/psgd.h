@@ -874,6 +874,35 @@ int psgd_aggregate_mixed_comm_adam_wide(psgd_plan* plan, void* const* grads_bf16
                                         void* const* unc_vs, psgd_comm* comm, void* stream);
 int psgd_plan_mixed_adam_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok);
 
+/* ------- the fused SGD step at ranks 33-128 (a wide plan, psgd_plan_is_wide) ------- */
+/* psgd_aggregate_comm_sgd_wide: psgd_aggregate_comm_sgd's arguments on a wide plan, which that entry
+ * refuses. DEFINED against the slab, as the wide Adam entries, and equal to it bit for bit (every p,
+ * buf, the residual, the P/Q state; the same collectives in order and count):
+ *   1. psgd_aggregate_comm(plan, grads, out, step, flat, unc, flat_out, comm) into scratch slabs
+ *   2. psgd_sgd_update on those averages with params / bufs (then unc_params / unc_bufs) and hyper
+ * Where it runs: the final pass as k_wide_apply_sgd (psgd_wide_sgd.hip): k_wide_apply<float>'s tile
+ * and MFMA sequence with the factor blocks staged in LDS (psgd_aggregate_mixed_wide's pass), so the
+ * residual and the average g of an element have k_wide_apply's bits; at the element where g would
+ * have been stored, p and buf are read from the tensor's own buffers, take THE UPDATE of
+ * psgd_sgd_hyper and are stored back. A tile whose record has momentum == 0 runs a body that has no
+ * buffer operand: `bufs` / `unc_bufs` (or an entry) may be NULL or a placeholder there and is
+ * neither read nor written. A tile takes 16-byte accesses where m % 4 == 0 and p (with momentum:
+ * and buf) is 16-byte aligned, else 4-byte ones, chosen once per tile; every access is predicated on
+ * its own row and column, nothing outside the numel elements of a tensor is read or written. The
+ * flat tail is packed in a launch of its own, summed by the last collective into the plan's stage,
+ * and updated by the leading workgroups of the final launch. `comm` NULL: world size 1, no
+ * collectives.
+ * Eligible: an fp32 wide plan of one bucket both of whose instances (one rank: shared terms; else
+ * two term sets) are admitted (two waves per SIMD, no scratch; asked once per plan).
+ * psgd_plan_sgd_wide_ok: *ok = 1 for such a plan (`momentum_used` is validated only: the momentum
+ * branch is taken per tile). A refusal launches nothing and issues no collective.
+ * Refusals: psgd_aggregate_comm_sgd's codes in its order; a plan that is not wide: PSGD_ERR_VALUE.
+ * psgd_aggregate_comm_sgd and psgd_plan_sgd_ok keep refusing a wide plan. */
+int psgd_aggregate_comm_sgd_wide(psgd_plan* plan, void* const* grads, void* const* params, void* const* bufs,
+                                 const psgd_sgd_hyper* hyper, int64_t step, psgd_flat* flat, void* const* unc,
+                                 void* const* unc_params, void* const* unc_bufs, psgd_comm* comm, void* stream);
+int psgd_plan_sgd_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t momentum_used, int32_t* ok);
+
 /* ------- the DDP hook's one-call completions at ranks 33-128 (a wide plan, psgd_plan_is_wide) ------- */
 /* psgd_aggregate_comm_dst_wide: psgd_aggregate_comm_dst's arguments on a wide plan, which that entry
  * refuses. DEFINED as, and bit for bit equal to (every destination, the residual, the P/Q state; the

@@ -117,6 +117,8 @@ _SIGNATURES = {
     "psgd_plan_dst_wide_ok": ([_vp, _i64, _i32, _P_i32], _i32),
     "psgd_aggregate_mixed_comm_dst_wide": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_plan_mixed_dst_wide_ok": ([_vp, _i64, _i32, _P_i32], _i32),
+    "psgd_aggregate_comm_sgd_wide": ([_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_plan_sgd_wide_ok": ([_vp, _i64, _i32, _i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -439,14 +441,23 @@ class Plan:
         return int(ok.value)
 
     def aggregate_comm_sgd(self, grads, params, bufs, hyper, step: int, comm: Optional["Comm"], stream: int, flat=None,
-                           unc=None, unc_params=None, unc_bufs=None) -> None:
+                           unc=None, unc_params=None, unc_bufs=None, wide: bool = False) -> None:
         """psgd_aggregate_comm_sgd: ``aggregate_comm_dst`` followed by ``sgd_update`` in one call; the final
         pass applies the update to ``params[i]`` / ``bufs[i]`` (then the flat plan's) and stores no
         average. ``hyper``: ``sgd_hyper`` records, the plan's tensors then the flat plan's. ``comm`` None:
-        world size 1, no collectives."""
-        check(lib().psgd_aggregate_comm_sgd(self._h, grads, params, bufs, ctypes.addressof(hyper) if hyper is not None
-                                            else None, step, flat._h if flat is not None else None, unc, unc_params,
-                                            unc_bufs, comm._h if comm is not None else None, stream))
+        world size 1, no collectives. ``wide``: psgd_aggregate_comm_sgd_wide, the same on a plan of ranks
+        33-128 (``aggregate_comm`` followed by ``sgd_update``)."""
+        fn = lib().psgd_aggregate_comm_sgd_wide if wide else lib().psgd_aggregate_comm_sgd
+        check(fn(self._h, grads, params, bufs, ctypes.addressof(hyper) if hyper is not None else None, step,
+                 flat._h if flat is not None else None, unc, unc_params, unc_bufs,
+                 comm._h if comm is not None else None, stream))
+
+    def sgd_wide_ok(self, step: int, world: int, momentum_used: bool = True) -> int:
+        """1 where ``aggregate_comm_sgd(wide=True)`` serves this plan (psgd_plan_sgd_wide_ok: an fp32 wide
+        plan of one bucket whose k_wide_apply_sgd instances are admitted)."""
+        ok = _i32()
+        check(lib().psgd_plan_sgd_wide_ok(self._h, step, world, int(bool(momentum_used)), ctypes.byref(ok)))
+        return int(ok.value)
 
     # --- the fused Adam / AdamW step
     def adam_ok(self, step: int, world: int) -> int:

@@ -653,6 +653,19 @@ struct WideAdamDst {
 hipError_t launch_wide_apply_adam(int R, bool mp, const WideArgs& a, const WideAdamDst& x, int ntiles, hipStream_t s,
                                   int* waves);
 
+// psgd_aggregate_comm_sgd_wide (ranks 33-128): the same pass whose epilogue applies the SGD update
+// (include/psgd.h, THE UPDATE of psgd_sgd_hyper) at that element. `p` the parameters in the plan's
+// tensor order, `y` the momentum buffers (an entry is read only where its record's momentum != 0:
+// the tile then runs a body without a buffer operand), the flat plan's tables, the staged flat tail
+// and the records, `flat` the flat tail's update items, which lead the launch.
+struct WideSgdDst {
+    void* const* p;
+    SgdDst y;
+    FlatArgs flat;
+};
+// psgd_wide_sgd.hip. ntiles + items == 0: no launch; `*waves` as above.
+hipError_t launch_wide_apply_sgd(int R, const WideArgs& a, const WideSgdDst& x, int ntiles, hipStream_t s, int* waves);
+
 // psgd_aggregate_comm_dst_wide / psgd_aggregate_mixed_comm_dst_wide (ranks 33-128, the DDP hook's
 // completions): the same pass whose epilogue stores each tensor's average at the tensor's own
 // destination (a view into a DDP bucket: dense; fp32 4-byte aligned or better, bf16 2-byte) at the

@@ -25,6 +25,8 @@
 //   wide adam    psgd_aggregate_comm_adam_wide / psgd_aggregate_mixed_comm_adam_wide (ranks 33-128): the two
 //                above with psgd_aggregate_comm's slabs in place of the scratch destinations (a wide plan
 //                has no destination-table step); the final pass is k_wide_apply_adam.
+//   wide sgd     psgd_aggregate_comm_sgd_wide (ranks 33-128): psgd_aggregate_comm into scratch slabs, then
+//                psgd_sgd_update on them; the final pass is k_wide_apply_sgd.
 //   wide tables  psgd_aggregate_comm_dst_wide / psgd_aggregate_mixed_comm_dst_wide (ranks 33-128), the DDP
 //                hook's completions on a wide plan: psgd_aggregate_comm into scratch slabs, then every
 //                average copied (bf16: rounded) to the tensor's own destination; the final pass is
@@ -54,6 +56,7 @@ struct Entry {
     Adm::Kind kind() const {
         if (wide_dst()) return bf16 ? Adm::Bf16TablesWide : Adm::F32TablesWide;
         if (adam && wide) return mp ? Adm::F32AdamMpWide : Adm::F32AdamWide;
+        if (sgd && wide) return Adm::F32SgdWide;
         return mp ? Adm::F32AdamMp : adam ? Adm::F32Adam : sgd ? Adm::F32Sgd : !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense;
     }
 };
@@ -125,6 +128,13 @@ const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool
         }
         if (p->wide()) return "psgd_aggregate_comm_adam serves rank buckets 1 to 32";
         if (p->spans.size() > 1) return "psgd_aggregate_comm_adam takes a plan of one bucket";
+    } else if (sgd && wide) {  // the wide SGD entry: what the narrow one refuses by rank
+        if (p->dtype != PSGD_F32) {
+            *code = PSGD_ERR_DTYPE;
+            return "psgd_aggregate_comm_sgd_wide takes an fp32 plan";
+        }
+        if (!p->wide()) return "psgd_aggregate_comm_sgd_wide serves ranks 33-128 (psgd_aggregate_comm_sgd: rank buckets 1 to 32)";
+        if (p->spans.size() > 1) return "psgd_aggregate_comm_sgd_wide takes a plan of one bucket";
     } else if (sgd) {
         if (p->dtype != PSGD_F32) {
             *code = PSGD_ERR_DTYPE;
@@ -159,8 +169,8 @@ const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool
 // communicator kind, asked with ntiles = 0 through the launch functions the drivers use. NoComm is
 // aggregate_ctx's context (the fused final pass where the step has one); Bf16Ingest its single-pass
 // final kernel with the ingest fold (false where the step's first pass is another one). A wide
-// plan's sink instances are k_wide_apply_mix<rbucket>, k_wide_apply_adam<rbucket> and
-// k_wide_apply_dst<rbucket> (shared terms at world size 1)
+// plan's sink instances are k_wide_apply_mix<rbucket>, k_wide_apply_adam<rbucket>,
+// k_wide_apply_sgd<rbucket> and k_wide_apply_dst<rbucket> (shared terms at world size 1)
 bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
     OutSink sink;
     sink.sgd = kind == Adm::F32Sgd;
@@ -177,6 +187,8 @@ bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
         if (kind == Adm::Bf16Dense) e = launch_wide_apply_mix(p->rbucket, a, 0, nullptr, &w);
         else if (kind == Adm::F32AdamWide || kind == Adm::F32AdamMpWide)
             e = launch_wide_apply_adam(p->rbucket, kind == Adm::F32AdamMpWide, a, WideAdamDst{}, 0, nullptr, &w);
+        else if (kind == Adm::F32SgdWide)
+            e = launch_wide_apply_sgd(p->rbucket, a, WideSgdDst{}, 0, nullptr, &w);
         else if (kind == Adm::F32TablesWide || kind == Adm::Bf16TablesWide)
             e = launch_wide_apply_dst(p->rbucket, kind == Adm::Bf16TablesWide, a, WideDst{}, 0, nullptr, &w);
     } else if (comm == Adm::NoComm) {
@@ -219,7 +231,9 @@ bool eligible(psgd_plan* p, const Entry& e, int world) {
     if (e.via == Entry::World1 && !e.wide) return admitted(p, e.kind(), Adm::NoComm);
     // a wide plan has no destination-table instances: its Adam entries are defined against
     // psgd_aggregate_comm's slab, and ask for k_wide_apply_adam of the communicator kind alone; its
-    // destination-table entries likewise for k_wide_apply_dst
+    // destination-table entries likewise for k_wide_apply_dst. Its SGD entry serves the plans both
+    // of whose forms (k_wide_apply_sgd with shared terms and with two term sets) are admitted
+    if (e.wide && e.sgd) return admitted(p, e.kind(), Adm::One) && admitted(p, e.kind(), Adm::Many);
     if (e.wide && (e.adam || e.tables)) return admitted(p, e.kind(), world == 1 ? Adm::One : Adm::Many);
     // an update entry is defined as the destination-table step followed by psgd_sgd_update /
     // psgd_adam_update: it serves the plans whose destination instances are admitted too
@@ -464,6 +478,7 @@ const Entry kCommAdam{"psgd_aggregate_comm_adam", Entry::Comm, false, true, fals
 const Entry kMixedCommAdam{"psgd_aggregate_mixed_comm_adam", Entry::Comm, false, true, false, false, true, true};
 const Entry kCommAdamWide{"psgd_aggregate_comm_adam_wide", Entry::Comm, true, true, false, false, true};
 const Entry kMixedCommAdamWide{"psgd_aggregate_mixed_comm_adam_wide", Entry::Comm, true, true, false, false, true, true};
+const Entry kCommSgdWide{"psgd_aggregate_comm_sgd_wide", Entry::Comm, true, true, false, true};
 const Entry kCommDstWide{"psgd_aggregate_comm_dst_wide", Entry::Comm, true, true, false};
 const Entry kMixedCommDstWide{"psgd_aggregate_mixed_comm_dst_wide", Entry::Comm, true, true, true};
 
@@ -562,6 +577,25 @@ int psgd_aggregate_comm_sgd(psgd_plan* p, void* const* grads, void* const* param
     c.unc_bufs = unc_bufs;
     c.hyper = hyper;
     return run(kCommSgd, c);
+}
+
+int psgd_plan_sgd_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t momentum_used, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    if (momentum_used != 0 && momentum_used != 1) return fail(PSGD_ERR_VALUE, "momentum_used is 0 or 1");
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, false, true, &code, true)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kCommSgdWide, world) ? 1 : 0; });
+}
+
+int psgd_aggregate_comm_sgd_wide(psgd_plan* p, void* const* grads, void* const* params, void* const* bufs,
+                                 const psgd_sgd_hyper* hyper, int64_t step, psgd_flat* f, void* const* unc,
+                                 void* const* unc_params, void* const* unc_bufs, psgd_comm* comm, void* stream) {
+    Call c{p, grads, params, nullptr, step, f, unc, unc_params, nullptr, comm, stream};
+    c.bufs = bufs;
+    c.unc_bufs = unc_bufs;
+    c.hyper = hyper;
+    return run(kCommSgdWide, c);
 }
 
 int psgd_plan_adam_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok) {

@@ -425,7 +425,8 @@ struct psgd_plan {
             F32AdamWide /* k_wide_apply_adam of psgd_aggregate_comm_adam_wide */,
             F32AdamMpWide /* its master-weight form, psgd_aggregate_mixed_comm_adam_wide */,
             F32TablesWide /* k_wide_apply_dst of psgd_aggregate_comm_dst_wide */,
-            Bf16TablesWide /* its bf16 form, psgd_aggregate_mixed_comm_dst_wide */, kKinds
+            Bf16TablesWide /* its bf16 form, psgd_aggregate_mixed_comm_dst_wide */,
+            F32SgdWide /* k_wide_apply_sgd of psgd_aggregate_comm_sgd_wide */, kKinds
         };
         enum Comm { NoComm /* aggregate_ctx */, Many /* world size > 1 */, One /* a 1-rank communicator */, kComms };
         uint64_t key = ~uint64_t(0);

@@ -222,7 +222,8 @@ int compress_wide(psgd_plan* p, void* const* grads, int64_t step, int32_t it, hi
 // A bf16 sink (psgd_aggregate_mixed_wide[_comm]): `grads` the fp32 residual, `out` bf16: the same
 // arguments to k_wide_apply_mix. An Adam sink (psgd_aggregate_comm_adam_wide, _mixed_comm_adam_wide):
 // no output; k_wide_apply_adam updates the sink's tensors, and the context's flat items (the flat
-// tail's update items) lead its launch. A destination-table sink (psgd_aggregate_comm_dst_wide,
+// tail's update items) lead its launch. An SGD sink (psgd_aggregate_comm_sgd_wide): likewise with
+// k_wide_apply_sgd. A destination-table sink (psgd_aggregate_comm_dst_wide,
 // _mixed_comm_dst_wide): no slab; k_wide_apply_dst stores each average at the sink's destination, and the
 // context's flat items (copy items, or a bf16 sink's round items) lead its launch
 int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, int32_t world, hipStream_t s,
@@ -248,6 +249,9 @@ int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, i
     if (sink && sink->adam) {
         WideAdamDst x{sink->dst, sink->adam_mp_dst(), c.fl ? *c.fl : FlatArgs{}};
         PSGD_HIP(launch_wide_apply_adam(p->rbucket, sink->adam_mp, a, x, int(p->wide_apply.size()), s, nullptr));
+    } else if (sink && sink->sgd) {
+        WideSgdDst x{sink->dst, sink->sgd_dst(), c.fl ? *c.fl : FlatArgs{}};
+        PSGD_HIP(launch_wide_apply_sgd(p->rbucket, a, x, int(p->wide_apply.size()), s, nullptr));
     } else if (sink && sink->tables) {
         WideDst x{sink->dst, sink->unc_dst, sink->stage, c.fl ? *c.fl : FlatArgs{}};
         PSGD_HIP(launch_wide_apply_dst(p->rbucket, sink->bf16, a, x, int(p->wide_apply.size()), s, nullptr));

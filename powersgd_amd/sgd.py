@@ -42,7 +42,8 @@ def sgd_step_applies(optimizer: torch.optim.Optimizer, aggregator: Aggregator) -
     """The NEXT ``sgd_step`` takes the one-call form: a plain ``torch.optim.SGD`` without ``maximize``,
     fp32 contiguous parameters on one device, a ``PowerSGD`` on a compressing step with neither
     ``max_grad_norm`` nor ``skip_nonfinite`` (both act on averages that would no longer exist), a
-    process group over the library's communicator, and a plan psgd_plan_sgd_ok serves.
+    process group over the library's communicator, and a plan psgd_plan_sgd_ok (ranks 33-128:
+    psgd_plan_sgd_wide_ok) serves.
     Not a pure query: the first call on a compressing step in a process group creates the library's
     communicator (``_rccl_comm``: a broadcast over the default group, a collective), so every rank
     calls it, or ``sgd_step``, at the same point, as ``PowerSGD.aggregate`` itself requires. The two
@@ -66,7 +67,8 @@ def sgd_step_applies(optimizer: torch.optim.Optimizer, aggregator: Aggregator) -
     if comm is None:
         return False
     plan = aggregator._powersgd._plan
-    return plan.sgd_ok(0, comm.world) == 1 and plan.sgd_ok(1, comm.world) == 1
+    ok = plan.sgd_wide_ok if plan.is_wide() else plan.sgd_ok  # ranks 33-128: psgd_aggregate_comm_sgd_wide
+    return ok(0, comm.world) == 1 and ok(1, comm.world) == 1
 
 
 def _records(optimizer: torch.optim.SGD, params: List[torch.Tensor]):
@@ -120,5 +122,6 @@ def sgd_step(optimizer: torch.optim.Optimizer, aggregator: Aggregator) -> None:
         kw = dict(flat=aggregator._unc.plan, unc=aggregator._table.unc_addr(), unc_params=ptab.unc_addr(),
                   unc_bufs=btab.unc_addr())
     codec._plan.aggregate_comm_sgd(aggregator._table.comp_addr(), ptab.comp_addr(), btab.comp_addr(), hyper,
-                                   codec.step_counter, comm, _stream(aggregator.device), **kw)
+                                   codec.step_counter, comm, _stream(aggregator.device), wide=codec._plan.is_wide(),
+                                   **kw)
     codec.step_counter += 1

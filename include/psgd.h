@@ -903,6 +903,76 @@ int psgd_aggregate_comm_sgd_wide(psgd_plan* plan, void* const* grads, void* cons
                                  void* const* unc_params, void* const* unc_bufs, psgd_comm* comm, void* stream);
 int psgd_plan_sgd_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t momentum_used, int32_t* ok);
 
+/* ------- the fused SGD step of a bf16 model with fp32 master weights and fp32 momentum buffers ------- */
+/* psgd_sgd_update_mp: psgd_sgd_update plus w_bf16[i][e] = bf16(p'[e]), in one launch
+ * (k_sgd_update_mp): p[i] are the fp32 master weights, w_bf16[i] the bf16 model tensors of numel[i]
+ * elements each. psgd_sgd_hyper and THE UPDATE are psgd_sgd_update's (every operation rounded to fp32
+ * on its own; with momentum == 0 the buffer is neither read nor written). The rounding of w is
+ * psgd_adam_update_mp's: round to nearest even of the stored fp32 p'. The same work items (at most
+ * 4096 elements, 64-bit offsets). The vector form applies to an item where g, p (with momentum: and
+ * buf) agree modulo 16 bytes and w is 8-byte aligned at the element where they reach their 16-byte
+ * boundary (16-byte accesses, 8-byte stores of w); any other item runs as 4-byte accesses with 2-byte
+ * stores of w. Every access goes through a descriptor over the item's own elements and every load is
+ * issued before the first store: nothing outside the numel elements of p[i] / buf[i] / w_bf16[i] is
+ * written, g is only read.
+ * Refusals: psgd_sgd_update's, in its order; a null w_bf16 with the null arguments, a null
+ * w_bf16[i] with the null tensor pointers (PSGD_ERR_VALUE); a w_bf16[i] that is not 2-byte aligned:
+ * PSGD_ERR_LAYOUT. */
+int psgd_sgd_update_mp(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* buf,
+                       void* const* w_bf16, const int64_t* numel, const psgd_sgd_hyper* hyper, void* stream);
+
+/* psgd_aggregate_mixed_comm_sgd: the SGD step of a bf16 model whose optimizer runs on fp32 master
+ * weights, in one call; psgd_aggregate_mixed_comm_adam's arguments with `bufs` / `unc_bufs` in place of
+ * the two moment tables and psgd_sgd_hyper records. bf16 gradients feed the fp32 error-feedback
+ * residual; the final pass of the codec, at the element where it would have stored the average,
+ * applies THE UPDATE to the master weight and the momentum buffer, stores both and stores the new
+ * weight rounded to bf16 at the model parameter's own address: 18 bytes per element with momentum
+ * (10 without) where the unfused step moves about 30. DEFINED as this sequence and equal to it bit
+ * for bit (every master, buffer, bf16 weight, residual, P/Q state, the zeroed gradients; the same
+ * collectives in order and count):
+ *   1. the ADD over every tensor: residual += float(g); g = +0.0 (psgd_runs_add_list, zero_source)
+ *   2. psgd_aggregate_comm_dst(plan, residual, dst, step, flat, unc_residual, unc_dst, comm) into
+ *      scratch destinations
+ *   3. psgd_sgd_update_mp on those averages with masters / bufs / params_bf16 (then the unc_*)
+ * Where it runs: the ADD is the first launch (two where there is a flat tail); the final pass of
+ * step 2 as its master-weight instance (psgd_sgd_mp_dst.hip: k_apply_sgd_mp, k_lowrank_sgd_mp),
+ * psgd_aggregate_comm_sgd's with a third descriptor over the tile's rows of the model tensor in
+ * 2-byte elements. A tile takes 16-byte accesses and one 8-byte store of w per row quad where its
+ * first element is 16-byte aligned in p (with momentum: and buf) and 8-byte aligned in w, else
+ * 4-byte accesses and four 2-byte stores of w; chosen once per tile. The leading workgroups of the
+ * final launch apply THE UPDATE to the flat plan's tensors from the stage.
+ * Eligible: psgd_plan_sgd_ok's rule, and the master-weight instances of the plan's final passes
+ * admitted too (two waves per SIMD, no scratch; asked of the runtime once per plan and tiling).
+ * psgd_plan_mixed_sgd_ok: *ok = 1 for such a plan. Rank bucket 8 with 2 or 3 iterations is refused,
+ * and so is a wide plan. A refusal launches nothing and issues no collective.
+ * Refusals: psgd_aggregate_comm_sgd's codes in its order (`residual` its grads, `masters` its
+ * params; a null grads_bf16 / params_bf16: "null argument"), then a null bf16 gradient or model
+ * parameter: PSGD_ERR_VALUE, one that is not 2-byte aligned: PSGD_ERR_LAYOUT. */
+int psgd_aggregate_mixed_comm_sgd(psgd_plan* plan, void* const* grads_bf16, void* const* residual,
+                                  void* const* params_bf16, void* const* masters, void* const* bufs,
+                                  const psgd_sgd_hyper* hyper, int64_t step, psgd_flat* flat, void* const* unc_bf16,
+                                  void* const* unc_residual, void* const* unc_params_bf16, void* const* unc_masters,
+                                  void* const* unc_bufs, psgd_comm* comm, void* stream);
+int psgd_plan_mixed_sgd_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t momentum_used, int32_t* ok);
+
+/* psgd_aggregate_mixed_comm_sgd_wide: the same arguments on a wide plan (ranks 33-128), which that
+ * entry refuses; this one refuses a plan that is not wide. DEFINED as, and bit for bit equal to: the
+ * ADD over every tensor, psgd_aggregate_comm on the residual into scratch slabs, psgd_sgd_update_mp
+ * on those averages. The final pass is k_wide_apply_sgd_mp (psgd_wide_sgd.hip), the master-weight
+ * form of k_wide_apply_sgd: it also stores bf16(p') at the model tensor, 8 bytes per row quad where
+ * m % 4 == 0 and the tensor is 8-byte aligned, else in 2-byte pieces; a tile whose momentum is 0
+ * keeps the body without a buffer operand; every access is predicated on its own row and column.
+ * Eligibility, the query and the refusals as psgd_aggregate_comm_sgd_wide's, with
+ * psgd_aggregate_mixed_comm_sgd's checks of the bf16 side. */
+int psgd_aggregate_mixed_comm_sgd_wide(psgd_plan* plan, void* const* grads_bf16, void* const* residual,
+                                       void* const* params_bf16, void* const* masters, void* const* bufs,
+                                       const psgd_sgd_hyper* hyper, int64_t step, psgd_flat* flat,
+                                       void* const* unc_bf16, void* const* unc_residual,
+                                       void* const* unc_params_bf16, void* const* unc_masters, void* const* unc_bufs,
+                                       psgd_comm* comm, void* stream);
+int psgd_plan_mixed_sgd_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t momentum_used,
+                                int32_t* ok);
+
 /* ------- the DDP hook's one-call completions at ranks 33-128 (a wide plan, psgd_plan_is_wide) ------- */
 /* psgd_aggregate_comm_dst_wide: psgd_aggregate_comm_dst's arguments on a wide plan, which that entry
  * refuses. DEFINED as, and bit for bit equal to (every destination, the residual, the P/Q state; the

@@ -14,7 +14,8 @@ from powersgd_amd.residual import Fp32ResidualPowerSGD  # noqa: F401
 from powersgd_amd.utils import params_in_optimizer
 
 __all__ = ["Aggregator", "AllReduce", "Config", "Fp32ResidualPowerSGD", "PowerSGD", "optimizer_step", "sgd_step",
-           "sgd_step_applies", "adam_step", "adam_step_applies", "adam_master_step", "adam_master_step_applies"]
+           "sgd_step_applies", "adam_step", "adam_step_applies", "adam_master_step", "adam_master_step_applies", "sgd_master_step",
+           "sgd_master_step_applies"]
 
 
 def optimizer_step(optimizer: torch.optim.Optimizer, aggregator: Aggregator):
@@ -40,3 +41,4 @@ def optimizer_step(optimizer: torch.optim.Optimizer, aggregator: Aggregator):
 from powersgd_amd.sgd import sgd_step, sgd_step_applies  # noqa: E402,F401  (uses optimizer_step above)
 from powersgd_amd.adam import adam_step, adam_step_applies  # noqa: E402,F401
 from powersgd_amd.adam_master import adam_master_step, adam_master_step_applies  # noqa: E402,F401
+from powersgd_amd.sgd_master import sgd_master_step, sgd_master_step_applies  # noqa: E402,F401

@@ -119,6 +119,11 @@ _SIGNATURES = {
     "psgd_plan_mixed_dst_wide_ok": ([_vp, _i64, _i32, _P_i32], _i32),
     "psgd_aggregate_comm_sgd_wide": ([_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     "psgd_plan_sgd_wide_ok": ([_vp, _i64, _i32, _i32, _P_i32], _i32),
+    "psgd_sgd_update_mp": ([_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    "psgd_aggregate_mixed_comm_sgd": ([_vp] * 7 + [_i64] + [_vp] * 8, _i32),
+    "psgd_plan_mixed_sgd_ok": ([_vp, _i64, _i32, _i32, _P_i32], _i32),
+    "psgd_aggregate_mixed_comm_sgd_wide": ([_vp] * 7 + [_i64] + [_vp] * 8, _i32),
+    "psgd_plan_mixed_sgd_wide_ok": ([_vp, _i64, _i32, _i32, _P_i32], _i32),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -148,6 +153,14 @@ def sgd_update(plan: Optional["Plan"], g, p, buf, numel: Sequence[int], hyper, s
     n = len(numel)
     check(lib().psgd_sgd_update(plan._h if plan is not None else None, n, g, p, buf, (_i64 * max(1, n))(*numel),
                                 ctypes.addressof(hyper), stream))
+
+
+def sgd_update_mp(plan: Optional["Plan"], g, p, buf, w_bf16, numel: Sequence[int], hyper, stream: int) -> None:
+    """psgd_sgd_update_mp: ``sgd_update`` on fp32 master weights ``p``, and ``w_bf16[i] = bf16(p'[i])`` for the
+    bf16 model tensors, in the same launch."""
+    n = len(numel)
+    check(lib().psgd_sgd_update_mp(plan._h if plan is not None else None, n, g, p, buf, w_bf16,
+                                   (_i64 * max(1, n))(*numel), ctypes.addressof(hyper), stream))
 
 
 class AdamHyper(ctypes.Structure):  # psgd_adam_hyper (include/psgd.h)
@@ -458,6 +471,33 @@ class Plan:
         ok = _i32()
         check(lib().psgd_plan_sgd_wide_ok(self._h, step, world, int(bool(momentum_used)), ctypes.byref(ok)))
         return int(ok.value)
+
+    # --- the fused SGD step of a bf16 model with fp32 master weights
+    def mixed_sgd_ok(self, step: int, world: int, momentum_used: bool = True) -> int:
+        """1 where ``aggregate_mixed_comm_sgd`` serves this plan (psgd_plan_mixed_sgd_ok: ``sgd_ok``'s rule and
+        the master-weight instances admitted), 0 for a plan it refuses."""
+        ok = _i32()
+        check(lib().psgd_plan_mixed_sgd_ok(self._h, step, world, int(bool(momentum_used)), ctypes.byref(ok)))
+        return int(ok.value)
+
+    def mixed_sgd_wide_ok(self, step: int, world: int, momentum_used: bool = True) -> int:
+        """``sgd_wide_ok`` for the master-weight form (psgd_plan_mixed_sgd_wide_ok)."""
+        ok = _i32()
+        check(lib().psgd_plan_mixed_sgd_wide_ok(self._h, step, world, int(bool(momentum_used)), ctypes.byref(ok)))
+        return int(ok.value)
+
+    def aggregate_mixed_comm_sgd(self, grads_bf16, residual, params_bf16, masters, bufs, hyper, step: int,
+                                 comm: Optional["Comm"], stream: int, flat=None, unc_bf16=None, unc_residual=None,
+                                 unc_params_bf16=None, unc_masters=None, unc_bufs=None, wide: bool = False) -> None:
+        """psgd_aggregate_mixed_comm_sgd: the ADD of the bf16 gradients into ``residual``,
+        ``aggregate_comm_dst`` on it and ``sgd_update_mp`` in one call: the final pass updates
+        ``masters[i]`` / ``bufs[i]`` and stores ``params_bf16[i] = bf16(masters[i])``. ``wide``:
+        psgd_aggregate_mixed_comm_sgd_wide, the same on a plan of ranks 33-128."""
+        fn = lib().psgd_aggregate_mixed_comm_sgd_wide if wide else lib().psgd_aggregate_mixed_comm_sgd
+        check(fn(self._h, grads_bf16, residual, params_bf16, masters, bufs,
+                 ctypes.addressof(hyper) if hyper is not None else None, step, flat._h if flat is not None else None,
+                 unc_bf16, unc_residual, unc_params_bf16, unc_masters, unc_bufs,
+                 comm._h if comm is not None else None, stream))
 
     # --- the fused Adam / AdamW step
     def adam_ok(self, step: int, world: int) -> int:

@@ -33,11 +33,11 @@ from .sgd import _comm_or_none
 from .utils import params_in_optimizer
 
 
-def _paired(optimizer: torch.optim.Optimizer, model_params: Sequence[torch.Tensor]):
+def _paired(optimizer: torch.optim.Optimizer, model_params: Sequence[torch.Tensor], who: str = "adam_master_step"):
     masters = params_in_optimizer(optimizer)
     model = list(model_params)
     if len(masters) != len(model) or any(a.shape != b.shape for a, b in zip(masters, model)):
-        raise ValueError("adam_master_step: the optimizer's master parameters and model_params must pair one to one, "
+        raise ValueError(f"{who}: the optimizer's master parameters and model_params must pair one to one, "
                          "in order and shape")
     return masters, model
 

@@ -21,18 +21,9 @@ struct psgd_plan::Adam {
     // own, so a plan that mixes both forms re-binds nothing; and the ADD of the flat plan's tensors
     // (bf16 gradients into their fp32 residual), a run table over that plan's element counts
     WordTable mp_tab, mp_hyper, sink_w;
-    psgd_runs* unc_add = nullptr;
-    char* unc_add_ws = nullptr;
-    std::vector<int64_t> unc_add_numel;
-    void drop_unc_add() {
-        if (unc_add) (void)psgd_runs_destroy(unc_add);
-        if (unc_add_ws) (void)hipFree(unc_add_ws);
-        unc_add = nullptr;
-        unc_add_ws = nullptr;
-    }
+    psgd::FlatAdd unc_add;
     ~Adam() {
         if (stage) (void)hipFree(stage);
-        drop_unc_add();
     }
 };
 
@@ -116,26 +107,7 @@ int adam_mp_check(const psgd_plan* p, void* const* grads16, void* const* ws, con
 int adam_mp_add(psgd_plan* p, const psgd_flat* f, void* const* unc16, void* const* unc_residual, hipStream_t s) {
     if (!f) return PSGD_OK;
     if (!p->adam) p->adam = new psgd_plan::Adam();
-    psgd_plan::Adam& m = *p->adam;
-    const size_t nu = size_t(f->count);
-    std::vector<int64_t> numel(nu, 0);
-    for (const FlatEntry& en : f->entries) numel[size_t(en.tensor)] = en.numel;
-    if (!m.unc_add || m.unc_add_numel != numel) {
-        if (m.unc_add) PSGD_HIP(hipStreamSynchronize(s));
-        m.drop_unc_add();
-        std::vector<int64_t> zero(nu, 0);
-        std::vector<int32_t> idx(nu);
-        for (size_t i = 0; i < nu; ++i) idx[i] = int32_t(i);
-        if (int st = psgd_runs_create_mixed(zero.data(), idx.data(), zero.data(), numel.data(), idx.data(), int32_t(nu),
-                                            int32_t(nu), int32_t(nu), PSGD_BF16, PSGD_F32, &m.unc_add))
-            return st;
-        int64_t rb = 0;
-        if (int st = psgd_runs_workspace_bytes(m.unc_add, &rb)) return st;
-        PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&m.unc_add_ws), size_t(std::max<int64_t>(rb, 1))));
-        if (int st = psgd_runs_bind(m.unc_add, p->device, m.unc_add_ws)) return st;
-        m.unc_add_numel = numel;
-    }
-    return psgd_runs_add_list(m.unc_add, unc16, unc_residual, 1, s);
+    return p->adam->unc_add.add(p->device, f, unc16, unc_residual, s);
 }
 
 int adam_mp_select(psgd_plan* p, void* const* ws, const psgd_flat* f, void* const* unc_ws, hipStream_t s, OutSink* sink) {

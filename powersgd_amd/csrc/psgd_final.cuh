@@ -658,12 +658,14 @@ constexpr int kLowrankUR = PSGD_LOWRANK_UR;
 // kDstAdamVec / kDstAdamElem (psgd_aggregate_comm_adam): the Adam forms; this tile caches P rows
 // only (61-129 VGPRs as an SGD form), so p, m and v all go out ahead of the row's term chain
 // kDstAdamMpVec / kDstAdamMpElem (psgd_aggregate_mixed_comm_adam): the same, and bf16(p') stored
+// kDstSgdMpVec / kDstSgdMpElem (psgd_aggregate_mixed_comm_sgd): the SGD forms, and bf16(p') stored
 template <typename T, int R, int NI, int V, int DST = 0>
 __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& d, const Tile& t,
                                              const SgdTile* sg = nullptr, const AdamTile* ad = nullptr) {
     constexpr bool SGD = is_sgd_dst(DST);
     constexpr bool ADAM = is_adam_dst(DST);
     constexpr bool MP = is_adam_mp_dst(DST);  // the master-weight forms: ad is an AdamMpTile, rW its bf16 tensor
+    constexpr bool SMP = is_sgd_mp_dst(DST);  // the same of the SGD forms: sg is an SgdMpTile
     const TileGeom g = tile_geom<V>(d, t);
     const int r = d.r;
     T* obase;
@@ -681,6 +683,9 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
     rsrc_t rW = rO;
     if constexpr (MP)
         rW = make_rsrc(static_cast<const AdamMpTile*>(ad)->w + g.row_begin * g.m,
+                       uint32_t((g.row_end - g.row_begin) * g.m * 2));
+    if constexpr (SMP)
+        rW = make_rsrc(static_cast<const SgdMpTile*>(sg)->w + g.row_begin * g.m,
                        uint32_t((g.row_end - g.row_begin) * g.m * 2));
     const int nt = NI > 0 ? NI : a.nterms;
     constexpr int NC = NI > 0 ? NI : 1;
@@ -736,6 +741,7 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
                     else if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
                     else st_vec<T>(rO, off, o);
                     if constexpr (MP) adam_mp_st<DST, V>(rW, off / 2u, pv);  // 2-byte elements
+                    if constexpr (SMP) sgd_mp_st<DST, V>(rW, off / 2u, pv);
                 }
             }
         }
@@ -782,6 +788,7 @@ __device__ __forceinline__ void lowrank_tile(const ApplyArgs& a, const MatDesc& 
             else if constexpr (DST != 0) st_vec_dst<DST>(rO, off, o);
             else st_vec<T>(rO, off, o);
             if constexpr (MP) adam_mp_st<DST, V>(rW, off / 2u, pv);
+            if constexpr (SMP) sgd_mp_st<DST, V>(rW, off / 2u, pv);
         }
     }
 }

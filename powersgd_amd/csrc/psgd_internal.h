@@ -587,6 +587,25 @@ struct SgdArgs {
 };
 hipError_t launch_sgd_update(const SgdArgs& a, hipStream_t s);
 
+// psgd_aggregate_mixed_comm_sgd / psgd_sgd_update_mp: the SGD update of fp32 master weights whose bf16
+// model tensors take bf16(p') in the same pass. SgdDst / SgdArgs as above (p the masters) and the
+// model tensors' tables beside them: the existing kernels' argument blocks stay as they are.
+struct SgdMpDst {
+    SgdDst x;
+    void* const* ws;     // bf16 model tensors, the plan's tensor order
+    void* const* unc_w;  // the flat plan's
+};
+// psgd_sgd_mp_dst.hip
+hipError_t launch_apply_sgd_mp(int R, int nterms, bool shared, const ApplyArgs& a, const SgdMpDst& y, int ntiles,
+                               hipStream_t s, int* waves);
+hipError_t launch_lowrank_sgd_mp(int R, int nterms, const ApplyArgs& a, const SgdMpDst& y, int ntiles, hipStream_t s,
+                                 int* waves);
+struct SgdMpArgs {
+    SgdArgs a;
+    void* const* w;
+};
+hipError_t launch_sgd_update_mp(const SgdMpArgs& y, hipStream_t s);
+
 // psgd_aggregate_comm_adam: the same with the Adam update (include/psgd.h, THE UPDATE of
 // psgd_adam_hyper). The parameter table is ApplyArgs::odst; here the two moment tables (the plan's
 // tensor order), the flat plan's parameters and moments, the staged flat tail, and the records.
@@ -665,6 +684,15 @@ struct WideSgdDst {
 };
 // psgd_wide_sgd.hip. ntiles + items == 0: no launch; `*waves` as above.
 hipError_t launch_wide_apply_sgd(int R, const WideArgs& a, const WideSgdDst& x, int ntiles, hipStream_t s, int* waves);
+// psgd_aggregate_mixed_comm_sgd_wide: the master-weight form (k_wide_apply_sgd_mp, the same unit). `p`
+// the masters, y.ws / y.unc_w the bf16 model tensors that take bf16(p').
+struct WideSgdMpDst {
+    void* const* p;
+    SgdMpDst y;
+    FlatArgs flat;
+};
+hipError_t launch_wide_apply_sgd_mp(int R, const WideArgs& a, const WideSgdMpDst& x, int ntiles, hipStream_t s,
+                                    int* waves);
 
 // psgd_aggregate_comm_dst_wide / psgd_aggregate_mixed_comm_dst_wide (ranks 33-128, the DDP hook's
 // completions): the same pass whose epilogue stores each tensor's average at the tensor's own

@@ -27,6 +27,10 @@
 //                has no destination-table step); the final pass is k_wide_apply_adam.
 //   wide sgd     psgd_aggregate_comm_sgd_wide (ranks 33-128): psgd_aggregate_comm into scratch slabs, then
 //                psgd_sgd_update on them; the final pass is k_wide_apply_sgd.
+//   sgd master   psgd_aggregate_mixed_comm_sgd (and _wide on ranks 33-128): the ADD, then the fp32 update
+//                entry's sequence with psgd_sgd_update_mp: the final pass (k_apply_sgd_mp / k_lowrank_sgd_mp;
+//                k_wide_apply_sgd_mp) updates the fp32 master weights and momentum buffers and stores
+//                bf16(p') at the model parameters.
 //   wide tables  psgd_aggregate_comm_dst_wide / psgd_aggregate_mixed_comm_dst_wide (ranks 33-128), the DDP
 //                hook's completions on a wide plan: psgd_aggregate_comm into scratch slabs, then every
 //                average copied (bf16: rounded) to the tensor's own destination; the final pass is
@@ -49,14 +53,15 @@ struct Entry {
     bool sgd = false;  // the update sink: `peer` the parameters, Call::bufs / hyper beside them; a null
                        // communicator is world size 1 without collectives
     bool adam = false;  // the Adam update sink: Call::bufs / vs the two moments, Call::adam the records
-    bool mp = false;  // adam over fp32 master weights of a bf16 model: `state` the residual, `peer` the
-                      // masters, Call::grads16 / ws the bf16 gradients and model parameters
+    bool mp = false;  // adam or sgd over fp32 master weights of a bf16 model: `state` the residual, `peer`
+                      // the masters, Call::grads16 / ws the bf16 gradients and model parameters
     bool upd() const { return sgd || adam; }
     bool wide_dst() const { return wide && tables && !upd(); }  // the wide destination-table entries
     Adm::Kind kind() const {
         if (wide_dst()) return bf16 ? Adm::Bf16TablesWide : Adm::F32TablesWide;
         if (adam && wide) return mp ? Adm::F32AdamMpWide : Adm::F32AdamWide;
-        if (sgd && wide) return Adm::F32SgdWide;
+        if (sgd && wide) return mp ? Adm::F32SgdMpWide : Adm::F32SgdWide;
+        if (sgd && mp) return Adm::F32SgdMp;
         return mp ? Adm::F32AdamMp : adam ? Adm::F32Adam : sgd ? Adm::F32Sgd : !bf16 ? Adm::F32Tables : tables ? Adm::Bf16Tables : Adm::Bf16Dense;
     }
 };
@@ -170,10 +175,11 @@ const char* ineligible(const psgd_plan* p, bool bf16, bool wide, int* code, bool
 // aggregate_ctx's context (the fused final pass where the step has one); Bf16Ingest its single-pass
 // final kernel with the ingest fold (false where the step's first pass is another one). A wide
 // plan's sink instances are k_wide_apply_mix<rbucket>, k_wide_apply_adam<rbucket>,
-// k_wide_apply_sgd<rbucket> and k_wide_apply_dst<rbucket> (shared terms at world size 1)
+// k_wide_apply_sgd[_mp]<rbucket> and k_wide_apply_dst<rbucket> (shared terms at world size 1)
 bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
     OutSink sink;
-    sink.sgd = kind == Adm::F32Sgd;
+    sink.sgd = kind == Adm::F32Sgd || kind == Adm::F32SgdMp;
+    sink.sgd_mp = kind == Adm::F32SgdMp;
     sink.adam = kind == Adm::F32Adam || kind == Adm::F32AdamMp;
     sink.adam_mp = kind == Adm::F32AdamMp;
     sink.bf16 = kind != Adm::F32Tables && !sink.sgd && !sink.adam;
@@ -189,6 +195,8 @@ bool ask(const psgd_plan* p, Adm::Kind kind, Adm::Comm comm, int par) {
             e = launch_wide_apply_adam(p->rbucket, kind == Adm::F32AdamMpWide, a, WideAdamDst{}, 0, nullptr, &w);
         else if (kind == Adm::F32SgdWide)
             e = launch_wide_apply_sgd(p->rbucket, a, WideSgdDst{}, 0, nullptr, &w);
+        else if (kind == Adm::F32SgdMpWide)
+            e = launch_wide_apply_sgd_mp(p->rbucket, a, WideSgdMpDst{}, 0, nullptr, &w);
         else if (kind == Adm::F32TablesWide || kind == Adm::Bf16TablesWide)
             e = launch_wide_apply_dst(p->rbucket, kind == Adm::Bf16TablesWide, a, WideDst{}, 0, nullptr, &w);
     } else if (comm == Adm::NoComm) {
@@ -238,8 +246,10 @@ bool eligible(psgd_plan* p, const Entry& e, int world) {
     // an update entry is defined as the destination-table step followed by psgd_sgd_update /
     // psgd_adam_update: it serves the plans whose destination instances are admitted too
     if (e.upd() && !(admitted(p, Adm::F32Tables, Adm::Many) && admitted(p, Adm::F32Tables, Adm::One))) return false;
-    // the master-weight entry applies psgd_plan_adam_ok's rule, then asks for its own instances
-    if (e.mp && !(admitted(p, Adm::F32Adam, Adm::Many) && admitted(p, Adm::F32Adam, Adm::One))) return false;
+    // a master-weight entry applies psgd_plan_adam_ok's / psgd_plan_sgd_ok's rule, then asks for its
+    // own instances
+    const Adm::Kind base = e.adam ? Adm::F32Adam : Adm::F32Sgd;
+    if (e.mp && !(admitted(p, base, Adm::Many) && admitted(p, base, Adm::One))) return false;
     if (e.wide || !e.bf16) return admitted(p, e.kind(), Adm::Many) && admitted(p, e.kind(), Adm::One);
     return admitted(p, e.kind(), world == 1 ? Adm::One : Adm::Many);
 }
@@ -384,8 +394,14 @@ int body(const Entry& e, const Call& c, bool* refused) {
                 if (int st = psgd_runs_add_list(p->mixed->add, c.grads16, c.state, 1, s)) return st;
                 if (int st = adam_mp_add(p, f, c.unc_grads16, c.unc_state, s)) return st;
             }
-        } else if (int st = sgd_select(p, c.peer, c.bufs, f, c.unc_peer, c.unc_bufs, c.hyper, s, &sink)) {
-            return st;
+        } else {
+            if (int st = sgd_select(p, c.peer, c.bufs, f, c.unc_peer, c.unc_bufs, c.hyper, s, &sink)) return st;
+            if (e.mp) {  // as the Adam form above
+                if (int st = sgd_mp_select(p, c.ws, f, c.unc_ws, s, &sink)) return st;
+                if (int st = ensure(p, p->mixed, true)) return st;
+                if (int st = psgd_runs_add_list(p->mixed->add, c.grads16, c.state, 1, s)) return st;
+                if (int st = sgd_mp_add(p, f, c.unc_grads16, c.unc_state, s)) return st;
+            }
         }
         return aggregate_comm_ctx(p, c.state, c.step, f, c.unc_state, c.comm, s, sink);
     }
@@ -479,6 +495,8 @@ const Entry kMixedCommAdam{"psgd_aggregate_mixed_comm_adam", Entry::Comm, false,
 const Entry kCommAdamWide{"psgd_aggregate_comm_adam_wide", Entry::Comm, true, true, false, false, true};
 const Entry kMixedCommAdamWide{"psgd_aggregate_mixed_comm_adam_wide", Entry::Comm, true, true, false, false, true, true};
 const Entry kCommSgdWide{"psgd_aggregate_comm_sgd_wide", Entry::Comm, true, true, false, true};
+const Entry kMixedCommSgd{"psgd_aggregate_mixed_comm_sgd", Entry::Comm, false, true, false, true, false, true};
+const Entry kMixedCommSgdWide{"psgd_aggregate_mixed_comm_sgd_wide", Entry::Comm, true, true, false, true, false, true};
 const Entry kCommDstWide{"psgd_aggregate_comm_dst_wide", Entry::Comm, true, true, false};
 const Entry kMixedCommDstWide{"psgd_aggregate_mixed_comm_dst_wide", Entry::Comm, true, true, true};
 
@@ -596,6 +614,64 @@ int psgd_aggregate_comm_sgd_wide(psgd_plan* p, void* const* grads, void* const* 
     c.unc_bufs = unc_bufs;
     c.hyper = hyper;
     return run(kCommSgdWide, c);
+}
+
+int psgd_plan_mixed_sgd_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t momentum_used, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    if (momentum_used != 0 && momentum_used != 1) return fail(PSGD_ERR_VALUE, "momentum_used is 0 or 1");
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, false, false, &code, true)) return PSGD_OK;
+    // rank bucket 8 with 2 or 3 iterations: its update instances are the ones no fused step admits
+    // (the register-cached two-set tile at the scratch edge); answered here without asking the device
+    if (plan->rbucket == 8 && (plan->iters == 2 || plan->iters == 3)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kMixedCommSgd, world) ? 1 : 0; });
+}
+
+int psgd_plan_mixed_sgd_wide_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t momentum_used, int32_t* ok) {
+    if (int st = query_args(plan && ok, step, world)) return st;
+    if (momentum_used != 0 && momentum_used != 1) return fail(PSGD_ERR_VALUE, "momentum_used is 0 or 1");
+    *ok = 0;
+    int code = 0;
+    if (ineligible(plan, false, true, &code, true)) return PSGD_OK;
+    return query(plan, [&](psgd_plan* p) { *ok = eligible(p, kMixedCommSgdWide, world) ? 1 : 0; });
+}
+
+namespace {
+
+int mixed_comm_sgd(const Entry& e, psgd_plan* p, void* const* grads_bf16, void* const* residual, void* const* params_bf16,
+                   void* const* masters, void* const* bufs, const psgd_sgd_hyper* hyper, int64_t step, psgd_flat* f,
+                   void* const* unc_bf16, void* const* unc_residual, void* const* unc_params_bf16,
+                   void* const* unc_masters, void* const* unc_bufs, psgd_comm* comm, void* stream) {
+    Call c{p, residual, masters, nullptr, step, f, unc_residual, unc_masters, nullptr, comm, stream};
+    c.bufs = bufs;
+    c.unc_bufs = unc_bufs;
+    c.hyper = hyper;
+    c.grads16 = grads_bf16;
+    c.unc_grads16 = unc_bf16;
+    c.ws = params_bf16;
+    c.unc_ws = unc_params_bf16;
+    return run(e, c);
+}
+
+}  // namespace
+
+int psgd_aggregate_mixed_comm_sgd(psgd_plan* p, void* const* grads_bf16, void* const* residual,
+                                  void* const* params_bf16, void* const* masters, void* const* bufs,
+                                  const psgd_sgd_hyper* hyper, int64_t step, psgd_flat* f, void* const* unc_bf16,
+                                  void* const* unc_residual, void* const* unc_params_bf16, void* const* unc_masters,
+                                  void* const* unc_bufs, psgd_comm* comm, void* stream) {
+    return mixed_comm_sgd(kMixedCommSgd, p, grads_bf16, residual, params_bf16, masters, bufs, hyper, step, f, unc_bf16,
+                          unc_residual, unc_params_bf16, unc_masters, unc_bufs, comm, stream);
+}
+
+int psgd_aggregate_mixed_comm_sgd_wide(psgd_plan* p, void* const* grads_bf16, void* const* residual,
+                                       void* const* params_bf16, void* const* masters, void* const* bufs,
+                                       const psgd_sgd_hyper* hyper, int64_t step, psgd_flat* f, void* const* unc_bf16,
+                                       void* const* unc_residual, void* const* unc_params_bf16,
+                                       void* const* unc_masters, void* const* unc_bufs, psgd_comm* comm, void* stream) {
+    return mixed_comm_sgd(kMixedCommSgdWide, p, grads_bf16, residual, params_bf16, masters, bufs, hyper, step, f,
+                          unc_bf16, unc_residual, unc_params_bf16, unc_masters, unc_bufs, comm, stream);
 }
 
 int psgd_plan_adam_ok(const psgd_plan* plan, int64_t step, int32_t world, int32_t* ok) {

@@ -426,7 +426,9 @@ struct psgd_plan {
             F32AdamMpWide /* its master-weight form, psgd_aggregate_mixed_comm_adam_wide */,
             F32TablesWide /* k_wide_apply_dst of psgd_aggregate_comm_dst_wide */,
             Bf16TablesWide /* its bf16 form, psgd_aggregate_mixed_comm_dst_wide */,
-            F32SgdWide /* k_wide_apply_sgd of psgd_aggregate_comm_sgd_wide */, kKinds
+            F32SgdWide /* k_wide_apply_sgd of psgd_aggregate_comm_sgd_wide */,
+            F32SgdMp /* the master-weight instances of psgd_aggregate_mixed_comm_sgd */,
+            F32SgdMpWide /* k_wide_apply_sgd_mp of psgd_aggregate_mixed_comm_sgd_wide */, kKinds
         };
         enum Comm { NoComm /* aggregate_ctx */, Many /* world size > 1 */, One /* a 1-rank communicator */, kComms };
         uint64_t key = ~uint64_t(0);
@@ -625,6 +627,9 @@ struct OutSink {
     void* const* ws = nullptr;
     void* const* unc_ws = nullptr;
     AdamMpDst adam_mp_dst() const { return AdamMpDst{adam_dst(), ws, unc_ws}; }
+    // psgd_aggregate_mixed_comm_sgd: `sgd` likewise over fp32 master weights, with the same model tables
+    bool sgd_mp = false;
+    SgdMpDst sgd_mp_dst() const { return SgdMpDst{sgd_dst(), ws, unc_ws}; }
     // the flat tail's bf16 gradients are added in the step, (x + float(g)) / W in a launch of its
     // own ahead of every collective; else the tail is packed as psgd_aggregate_comm packs it
     bool ingests() const { return bf16 && !tables; }
@@ -793,6 +798,10 @@ int adam_mp_check(const psgd_plan* p, void* const* grads16, void* const* ws, con
                   void* const* unc_ws);
 int adam_mp_add(psgd_plan* p, const psgd_flat* f, void* const* unc16, void* const* unc_residual, hipStream_t s);
 int adam_mp_select(psgd_plan* p, void* const* ws, const psgd_flat* f, void* const* unc_ws, hipStream_t s, OutSink* sink);
+// psgd_aggregate_mixed_comm_sgd (psgd_sgd.cpp): the bf16 side of the SGD sink. Its checks are
+// adam_mp_check's; sgd_mp_add and sgd_mp_select as the two above, on the SGD state, after sgd_select.
+int sgd_mp_add(psgd_plan* p, const psgd_flat* f, void* const* unc16, void* const* unc_residual, hipStream_t s);
+int sgd_mp_select(psgd_plan* p, void* const* ws, const psgd_flat* f, void* const* unc_ws, hipStream_t s, OutSink* sink);
 // psgd_step.cpp: the world-size-1 step of psgd_aggregate / psgd_aggregate_flat under `c`
 int aggregate_ctx(psgd_plan* p, void* const* grads, int64_t step, hipStream_t s, StepCtx c);
 // The world-size-W step into `sink`: over a communicator (psgd_step.cpp; `comm` null: world size 1,

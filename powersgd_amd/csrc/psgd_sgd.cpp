@@ -1,4 +1,4 @@
-// psgd_sgd_update (include/psgd.h) and the device tables of psgd_aggregate_comm_sgd's sink. Both keep
+// psgd_sgd_update / psgd_sgd_update_mp (include/psgd.h) and the device tables of psgd_aggregate_comm_sgd's sink. Both keep
 // their tables in a state of the plan's own (psgd_plan::Sgd, like Guard): word tables, a
 // TableCache over 8-byte words with a device allocation that grows on demand. What rarely changes
 // (pointers, work items) and what a learning-rate schedule changes every step (the records) are
@@ -27,6 +27,10 @@ struct psgd_plan::Sgd {
     float* stage = nullptr;  // fp32 stage of the flat tail (the flat plan's layout)
     size_t stage_cap = 0;
     std::vector<void*> words;  // scratch of a call: nothing is allocated once it has its size
+    // the master-weight forms (psgd_sgd_update_mp, psgd_aggregate_mixed_comm_sgd): tables of their
+    // own, so a plan that mixes both forms re-binds nothing; and the ADD of the flat plan's tensors
+    WordTable mp_tab, mp_hyper, sink_w;
+    psgd::FlatAdd unc_add;
     ~Sgd() {
         if (stage) (void)hipFree(stage);
     }
@@ -87,18 +91,41 @@ int sgd_select(psgd_plan* p, void* const* params, void* const* bufs, const psgd_
     return PSGD_OK;
 }
 
+int sgd_mp_add(psgd_plan* p, const psgd_flat* f, void* const* unc16, void* const* unc_residual, hipStream_t s) {
+    if (!f) return PSGD_OK;
+    return p->sgd->unc_add.add(p->device, f, unc16, unc_residual, s);  // after sgd_select
+}
+
+int sgd_mp_select(psgd_plan* p, void* const* ws, const psgd_flat* f, void* const* unc_ws, hipStream_t s, OutSink* sink) {
+    psgd_plan::Sgd& m = *p->sgd;  // after sgd_select
+    const size_t nt = p->shapes.size(), nu = f ? size_t(f->count) : 0;
+    std::vector<void*>& w = m.words;
+    w.clear();
+    put_ptrs(w, ws, nt);
+    put_ptrs(w, unc_ws, nu);
+    const void* tab = nullptr;
+    if (int st = m.sink_w.select(w, s, &tab)) return st;
+    void* const* t = static_cast<void* const*>(tab);
+    sink->sgd_mp = true;
+    sink->ws = t;
+    sink->unc_ws = t + nt;
+    return PSGD_OK;
+}
+
 }  // namespace psgd
 
 using namespace psgd;
 
-extern "C" int psgd_sgd_update(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* buf,
-                               const int64_t* numel, const psgd_sgd_hyper* hyper, void* stream) {
-    if (!g || !p || !numel || !hyper || count < 1) return fail(PSGD_ERR_VALUE, "null argument");
+// psgd_sgd_update (`mp` false: w unused) and psgd_sgd_update_mp (w[i] = bf16(p'[i]))
+static int sgd_update_any(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* buf,
+                          void* const* wt, bool mp, const int64_t* numel, const psgd_sgd_hyper* hyper, void* stream) {
+    if (!g || !p || (mp && !wt) || !numel || !hyper || count < 1) return fail(PSGD_ERR_VALUE, "null argument");
     if (plan && !plan->bound) return fail(PSGD_ERR_STATE, "plan is not bound to device memory");
     const size_t n = size_t(count);
     size_t nitems = 0;
     for (size_t i = 0; i < n; ++i) {
         if (!g[i] || !p[i]) return fail(PSGD_ERR_VALUE, "null tensor pointer");
+        if (mp && !wt[i]) return fail(PSGD_ERR_VALUE, "null bf16 model parameter pointer");
         if (hyper[i].momentum != 0.f && (!buf || !buf[i]))
             return fail(PSGD_ERR_VALUE, "null momentum buffer of a tensor with momentum");
         if (numel[i] < 0) return fail(PSGD_ERR_VALUE, "negative element count");
@@ -108,6 +135,8 @@ extern "C" int psgd_sgd_update(psgd_plan* plan, int32_t count, void* const* g, v
         const uintptr_t all = reinterpret_cast<uintptr_t>(g[i]) | reinterpret_cast<uintptr_t>(p[i]) |
                               reinterpret_cast<uintptr_t>(buf ? buf[i] : nullptr);
         if (all % 4) return fail(PSGD_ERR_LAYOUT, "averages, weights and momentum buffers must be 4-byte aligned");
+        if (mp && reinterpret_cast<uintptr_t>(wt[i]) % 2)
+            return fail(PSGD_ERR_LAYOUT, "bf16 model parameters must be 2-byte aligned");
     }
     if (nitems == 0) return PSGD_OK;
     if (nitems > size_t(INT32_MAX)) return fail(PSGD_ERR_VALUE, "too many work items");
@@ -116,9 +145,10 @@ extern "C" int psgd_sgd_update(psgd_plan* plan, int32_t count, void* const* g, v
     if (plan && !plan->sgd) plan->sgd = new psgd_plan::Sgd();
     psgd_plan::Sgd& m = plan ? *plan->sgd : local;
     DevScope scope(plan ? plan->device : -1);
-    // words: [g][p][buf][items]
+    // words: [g][p][buf][items], the master-weight form [w] ahead of them
     std::vector<void*>& w = m.words;
     w.clear();
+    if (mp) put_ptrs(w, wt, n);
     put_ptrs(w, g, n);
     put_ptrs(w, p, n);
     put_ptrs(w, buf, n);
@@ -129,12 +159,12 @@ extern "C" int psgd_sgd_update(psgd_plan* plan, int32_t count, void* const* g, v
             items.push_back(SgdItem{o, int32_t(i), int32_t(std::min<int64_t>(kRunItem, numel[i] - o))});
     put(w, items.data(), items.size() * sizeof(SgdItem));
     const void* tab = nullptr;
-    if (int st = m.upd_tab.select(w, s, &tab)) return st;
+    if (int st = (mp ? m.mp_tab : m.upd_tab).select(w, s, &tab)) return st;
     w.clear();
     put(w, hyper, n * sizeof(psgd_sgd_hyper));
     const void* hy = nullptr;
-    if (int st = m.upd_hyper.select(w, s, &hy)) return st;
-    void* const* t = static_cast<void* const*>(tab);
+    if (int st = (mp ? m.mp_hyper : m.upd_hyper).select(w, s, &hy)) return st;
+    void* const* t = static_cast<void* const*>(tab) + (mp ? n : 0);
     SgdArgs a{};
     a.g = t;
     a.p = t + n;
@@ -142,7 +172,18 @@ extern "C" int psgd_sgd_update(psgd_plan* plan, int32_t count, void* const* g, v
     a.items = reinterpret_cast<const SgdItem*>(t + 3 * n);
     a.hyper = static_cast<const psgd_sgd_hyper*>(hy);
     a.nitems = int32_t(nitems);
-    PSGD_HIP(launch_sgd_update(a, s));
+    if (mp) PSGD_HIP(launch_sgd_update_mp(SgdMpArgs{a, static_cast<void* const*>(tab)}, s));
+    else PSGD_HIP(launch_sgd_update(a, s));
     if (!plan) PSGD_HIP(hipStreamSynchronize(s));  // `local` (tables, pinned staging) goes with the call
     return PSGD_OK;
+}
+
+extern "C" int psgd_sgd_update(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* buf,
+                               const int64_t* numel, const psgd_sgd_hyper* hyper, void* stream) {
+    return sgd_update_any(plan, count, g, p, buf, nullptr, false, numel, hyper, stream);
+}
+
+extern "C" int psgd_sgd_update_mp(psgd_plan* plan, int32_t count, void* const* g, void* const* p, void* const* buf,
+                                  void* const* w_bf16, const int64_t* numel, const psgd_sgd_hyper* hyper, void* stream) {
+    return sgd_update_any(plan, count, g, p, buf, w_bf16, true, numel, hyper, stream);
 }

@@ -249,6 +249,9 @@ int decompress_wide(psgd_plan* p, void* const* grads, void* out, int64_t step, i
     if (sink && sink->adam) {
         WideAdamDst x{sink->dst, sink->adam_mp_dst(), c.fl ? *c.fl : FlatArgs{}};
         PSGD_HIP(launch_wide_apply_adam(p->rbucket, sink->adam_mp, a, x, int(p->wide_apply.size()), s, nullptr));
+    } else if (sink && sink->sgd_mp) {
+        WideSgdMpDst x{sink->dst, sink->sgd_mp_dst(), c.fl ? *c.fl : FlatArgs{}};
+        PSGD_HIP(launch_wide_apply_sgd_mp(p->rbucket, a, x, int(p->wide_apply.size()), s, nullptr));
     } else if (sink && sink->sgd) {
         WideSgdDst x{sink->dst, sink->sgd_dst(), c.fl ? *c.fl : FlatArgs{}};
         PSGD_HIP(launch_wide_apply_sgd(p->rbucket, a, x, int(p->wide_apply.size()), s, nullptr));
@@ -554,6 +557,9 @@ hipError_t psgd::launch_out_pass(const psgd_plan* p, const OutRoute& o, ApplyArg
                                                : launch_apply(p->dtype, R, I, o.shared, a, ntiles, s);
         if (p->dtype != PSGD_F32) return hipErrorInvalidValue;  // fp32 averages at the per-tensor destinations
         a.odst = sink->dst;
+        if (sink->sgd_mp)  // the SGD update of master weights, bf16(p') stored at the model tensors
+            return o.kind == OutRoute::Lowrank ? launch_lowrank_sgd_mp(R, I, a, sink->sgd_mp_dst(), ntiles, s, waves)
+                                               : launch_apply_sgd_mp(R, I, o.shared, a, sink->sgd_mp_dst(), ntiles, s, waves);
         if (sink->sgd)  // the update applied where the average would have been stored
             return o.kind == OutRoute::Lowrank ? launch_lowrank_sgd(R, I, a, sink->sgd_dst(), ntiles, s, waves)
                                                : launch_apply_sgd(R, I, o.shared, a, sink->sgd_dst(), ntiles, s, waves);

@@ -248,9 +248,21 @@ __device__ __forceinline__ void st_vec_dstf(rsrc_t r, uint32_t off, const float 
 // buffer and its tensor's record come in a SgdTile, built once per tile from workgroup-uniform
 // loads (the record lives in SGPRs, its branches are scalar).
 constexpr int kDstSgdVec = 3, kDstSgdElem = 4;
+// The master-weight forms (psgd_aggregate_mixed_comm_sgd, psgd_sgd_mp_dst.hip): the same update on the
+// fp32 master weight and buffer, and the new weight rounded to bf16 (round to nearest even,
+// bf16_pin_t) stored at the model parameter's own address through a third descriptor: the tile's
+// rows of the model tensor in 2-byte elements. kDstSgdMpVec: the tile's first element is 16-byte
+// aligned in p (with momentum: and buf) and 8-byte aligned in w (one 8-byte store per row quad);
+// kDstSgdMpElem: 4-byte accesses of p and buf and four 2-byte stores of w.
+constexpr int kDstSgdMpVec = 9, kDstSgdMpElem = 10;
+constexpr bool is_sgd_mp_dst(int dst) { return dst == kDstSgdMpVec || dst == kDstSgdMpElem; }
+constexpr bool is_sgd_elem(int dst) { return dst == kDstSgdElem || dst == kDstSgdMpElem; }
 struct SgdTile {
     float* buf;  // the tensor's momentum buffer; null where momentum == 0
     psgd_sgd_hyper h;
+};
+struct SgdMpTile : SgdTile {
+    uint16_t* w;  // the bf16 model tensor of the master weight a.odst names
 };
 // a product that exists as a rounded fp32 value of its own: the empty asm consumes it, so no
 // following add can contract it into an fma (the fused and the element-wise form agree bit for bit)
@@ -272,7 +284,7 @@ __device__ __forceinline__ void sgd_update(const psgd_sgd_hyper& h, float g, flo
 // a vector of p or buf at byte offset `off` of its descriptor (out of range: zeros, no access)
 template <int DST>
 __device__ __forceinline__ void sgd_ld(rsrc_t r, uint32_t off, float (&v)[4]) {
-    if constexpr (DST == kDstSgdElem) {
+    if constexpr (is_sgd_elem(DST)) {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             v[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off + 4u * uint32_t(e), 0, 0));
@@ -289,7 +301,7 @@ __device__ __forceinline__ void sgd_ld(rsrc_t r, uint32_t off, float (&v)[1]) {
 // plain stores (aux 0): p' is read by the next forward pass, buf' by the next step
 template <int DST>
 __device__ __forceinline__ void sgd_st(rsrc_t r, uint32_t off, const float (&v)[4]) {
-    if constexpr (DST == kDstSgdElem) StIo<float>::template st4e<0>(r, off, v);
+    if constexpr (is_sgd_elem(DST)) StIo<float>::template st4e<0>(r, off, v);
     else StIo<float>::template st4<0>(r, off, v);
 }
 template <int DST>
@@ -324,7 +336,16 @@ __device__ __forceinline__ void sgd_apply(const SgdTile& sg, rsrc_t rP, rsrc_t r
 __device__ __forceinline__ rsrc_t sgd_buf_rsrc(const SgdTile& sg, int64_t first, uint32_t bytes) {
     return make_rsrc(sg.buf ? sg.buf + first : nullptr, sg.buf ? bytes : 0u);
 }
-constexpr bool is_sgd_dst(int dst) { return dst == kDstSgdVec || dst == kDstSgdElem; }
+constexpr bool is_sgd_dst(int dst) { return dst == kDstSgdVec || dst == kDstSgdElem || is_sgd_mp_dst(dst); }
+// the master-weight forms' third store: bf16(p') of the values sgd_apply has just stored, at byte
+// offset `woff` of the model tensor's descriptor (2-byte elements; kOob: dropped). Plain stores: the
+// next forward pass reads them
+template <int DST, int V>
+__device__ __forceinline__ void sgd_mp_st(rsrc_t rW, uint32_t woff, const float (&pv)[V]) {
+    if constexpr (V == 1) StIo<bf16_pin_t>::template st1<0>(rW, woff, pv[0]);
+    else if constexpr (DST == kDstSgdMpElem) StIo<bf16_pin_t>::template st4e<0>(rW, woff, pv);
+    else StIo<bf16_pin_t>::template st4<0>(rW, woff, pv);
+}
 
 // The Adam update forms (psgd_aggregate_comm_adam, psgd_adam_dst.hip; TO = float): the same place in
 // the tile, with torch's single-tensor Adam / AdamW rule (include/psgd.h, THE UPDATE of
@@ -1411,6 +1432,7 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
     constexpr bool SGD = is_sgd_dst(DST);  // the update forms: rO spans the tile's rows of p, rB of buf
     constexpr bool ADAM = is_adam_dst(DST);  // rO spans p, rM / rV the two moments
     constexpr bool MP = is_adam_mp_dst(DST);  // rW the bf16 model tensor (ad is an AdamMpTile)
+    constexpr bool SMP = is_sgd_mp_dst(DST);  // the same of the SGD forms (sg is an SgdMpTile)
     // rows in flight per lane. The update forms of the two-set instances that cache 12 or more
     // factor columns per set keep 2: their destination twins sit at the register edge with 4
     // (k_apply_dst<4, 3, false>: 255 VGPRs), and p, buf and the update's temporaries do not fit
@@ -1440,6 +1462,9 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
     rsrc_t rW = rO;
     if constexpr (MP)
         rW = make_rsrc(static_cast<const AdamMpTile*>(ad)->w + g.row_begin * g.m,
+                       uint32_t((g.row_end - g.row_begin) * g.m * 2));
+    if constexpr (SMP)
+        rW = make_rsrc(static_cast<const SgdMpTile*>(sg)->w + g.row_begin * g.m,
                        uint32_t((g.row_end - g.row_begin) * g.m * 2));
     const int nt = NI > 0 ? NI : a.nterms;
     constexpr int NC = NI > 0 ? NI : 1;
@@ -1551,6 +1576,7 @@ __device__ __forceinline__ void apply_tile(const ApplyArgs& a, const MatDesc& d,
                 st_vec<T>(rD, eo * uint32_t(sizeof(T)), b.x[u]);
                 if constexpr (SGD) {
                     sgd_apply<DST, V>(*sg, rO, rB, eo * uint32_t(sizeof(float)), o, pv, bv);
+                    if constexpr (SMP) sgd_mp_st<DST, V>(rW, eo * 2u, pv);
                 } else if constexpr (ADAM) {
                     if constexpr (kAdamAhead < 1) sgd_ld<adam_io<DST>()>(rO, eo * 4u, pv);
                     if constexpr (kAdamAhead < 2) sgd_ld<adam_io<DST>()>(rM, eo * 4u, bv);
@@ -1606,6 +1632,7 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
     constexpr bool SGD = is_sgd_dst(DST);  // the update forms (T = TO = float): rO spans p, rB buf
     constexpr bool ADAM = is_adam_dst(DST);  // rO spans p, rM / rV the two moments
     constexpr bool MP = is_adam_mp_dst(DST);  // rW the bf16 model tensor (ad is an AdamMpTile)
+    constexpr bool SMP = is_sgd_mp_dst(DST);  // the same of the SGD forms (sg is an SgdMpTile)
     constexpr int KQ = R / 4;
     constexpr int RP = ApplyMfmaLds<R>::RP;
     constexpr int NS = SHARED ? 1 : 2;
@@ -1662,6 +1689,9 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
     rsrc_t rW = rO;
     if constexpr (MP)
         rW = make_rsrc(static_cast<const AdamMpTile*>(ad)->w + row_begin * m,
+                       uint32_t((row_end - row_begin) * int64_t(m) * 2));
+    if constexpr (SMP)
+        rW = make_rsrc(static_cast<const SgdMpTile*>(sg)->w + row_begin * m,
                        uint32_t((row_end - row_begin) * int64_t(m) * 2));
     const uint32_t cofs = active ? uint32_t(col) * s : kOob;
     const uint32_t rstride = uint32_t(m) * s;
@@ -1758,6 +1788,10 @@ __device__ __forceinline__ void apply_tile_mfma(const ApplyArgs& a, const MatDes
                 else st_vec<TO, ONT ? kStAuxOutNt : PSGD_ST_AUX>(rO, oo_off, oo);
             } else if constexpr (SGD) {
                 sgd_apply<DST, 4>(*sg, rO, rB, off, oo, pv[v], bv[v]);
+                if constexpr (SMP) {  // in 2-byte elements: in range or kOob, by the explicit test
+                    const bool in = active && b0 + 4 * cq + v < row_end;
+                    sgd_mp_st<DST, 4>(rW, in ? ((rb + v) * uint32_t(m) + uint32_t(col)) * 2u : kOob, pv[v]);
+                }
             } else if constexpr (ADAM) {
                 if constexpr (kAdamAheadMfma < 1) sgd_ld<adam_io<DST>()>(rO, off, pv[v]);
                 if constexpr (kAdamAheadMfma < 2) sgd_ld<adam_io<DST>()>(rM, off, bv[v]);

@@ -41,6 +41,43 @@ struct WordTable {
     ~WordTable() { release(); }
 };
 
+// The ADD of the flat plan's tensors in the master-weight entries (residual += float(g); g = +0.0):
+// a run table over that plan's element counts with its workspace, made at the first call and again
+// when the counts change
+struct FlatAdd {
+    psgd_runs* runs = nullptr;
+    char* ws = nullptr;
+    std::vector<int64_t> numel;
+    void drop() {
+        if (runs) (void)psgd_runs_destroy(runs);
+        if (ws) (void)hipFree(ws);
+        runs = nullptr;
+        ws = nullptr;
+    }
+    int add(int device, const psgd_flat* f, void* const* unc16, void* const* unc_residual, hipStream_t s) {
+        const size_t nu = size_t(f->count);
+        std::vector<int64_t> want(nu, 0);
+        for (const FlatEntry& en : f->entries) want[size_t(en.tensor)] = en.numel;
+        if (!runs || numel != want) {
+            if (runs) PSGD_HIP(hipStreamSynchronize(s));
+            drop();
+            std::vector<int64_t> zero(nu, 0);
+            std::vector<int32_t> idx(nu);
+            for (size_t i = 0; i < nu; ++i) idx[i] = int32_t(i);
+            if (int st = psgd_runs_create_mixed(zero.data(), idx.data(), zero.data(), want.data(), idx.data(), int32_t(nu),
+                                                int32_t(nu), int32_t(nu), PSGD_BF16, PSGD_F32, &runs))
+                return st;
+            int64_t rb = 0;
+            if (int st = psgd_runs_workspace_bytes(runs, &rb)) return st;
+            PSGD_HIP(hipMalloc(reinterpret_cast<void**>(&ws), size_t(rb > 1 ? rb : 1)));
+            if (int st = psgd_runs_bind(runs, device, ws)) return st;
+            numel = want;
+        }
+        return psgd_runs_add_list(runs, unc16, unc_residual, 1, s);
+    }
+    ~FlatAdd() { drop(); }
+};
+
 inline void put(std::vector<void*>& w, const void* src, size_t bytes) {
     const size_t at = w.size();
     w.resize(at + (bytes + sizeof(void*) - 1) / sizeof(void*), nullptr);

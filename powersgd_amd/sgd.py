@@ -38,6 +38,13 @@ def _comm_or_none(aggregator: PowerSGD):
     return codec._rccl_comm()
 
 
+def _options_served(optimizer: torch.optim.Optimizer) -> bool:
+    """Exactly ``torch.optim.SGD`` without ``maximize`` (THE UPDATE has no such form)."""
+    if type(optimizer) is not torch.optim.SGD:
+        return False
+    return not any(g.get("maximize", False) for g in optimizer.param_groups)
+
+
 def sgd_step_applies(optimizer: torch.optim.Optimizer, aggregator: Aggregator) -> bool:
     """The NEXT ``sgd_step`` takes the one-call form: a plain ``torch.optim.SGD`` without ``maximize``,
     fp32 contiguous parameters on one device, a ``PowerSGD`` on a compressing step with neither
@@ -48,9 +55,7 @@ def sgd_step_applies(optimizer: torch.optim.Optimizer, aggregator: Aggregator) -
     communicator (``_rccl_comm``: a broadcast over the default group, a collective), so every rank
     calls it, or ``sgd_step``, at the same point, as ``PowerSGD.aggregate`` itself requires. The two
     plan queries are answered from the plan's admission cache after the first call."""
-    if type(optimizer) is not torch.optim.SGD or type(aggregator) is not PowerSGD:
-        return False
-    if any(g.get("maximize", False) for g in optimizer.param_groups):
+    if not _options_served(optimizer) or type(aggregator) is not PowerSGD:
         return False
     params = params_in_optimizer(optimizer)
     dev = aggregator.device
